@@ -1,16 +1,21 @@
 """Headline benchmark: depth-maps/s of a full U-Net train step on synthetic BatVisionV2-shaped batches.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 Workload = BASELINE.json configs[1]: models.unetbaseline_model.define_G(unet_256, ngf 64) on 256x256
 two-channel inputs, bf16 MFMA compute, batch 32 PER GPU (weak scaling), one step = forward + masked
 Combined loss (conf/mode/train.yaml weights) + backward + [gradient all-reduce] + clip_grad_norm(1.0) +
-AdamW -- exactly /root/reference/train.py:633-691.  Inputs are resident in HBM when the timed region starts.
-Rank 0 prints ONE JSON line; it also carries
+AdamW -- exactly the reference's train.py:633-691.  Inputs are resident in HBM when the timed region starts.
+Rank 0 prints ONE JSON line: the headline (value, ms_per_step of the K timed steps) and final_loss.
+--dump-outputs DIR writes what the last timed step left its caller (rank 0), float32: loss.npy, pred.npy and a fixed,
+seeded sample of the updated parameters, params_sample.npy (dump_outputs).
+--full adds the measurements that take runs of their own:
   roofline:     the dominant kernel family (MFMA implicit GEMM) timed with HIP events on its own stream
-                inside the timed region, algorithmic FLOPs / time vs the bf16 dense MFMA peak;
+                just before the timed region, algorithmic FLOPs / time vs the bf16 dense MFMA peak;
+  sustained:    >= --sustain-seconds of back-to-back steps behind the timed region, per-step event times;
+  f32_exact:    the same step on the exact-f32 MFMA path (N=1, bf16 runs only);
   cpu_baseline: the CPU oracle (port of the reference's torch-CPU path) timed on this box's host cores
                 on a bounded sample (rank 0, N=1 only).
 """
@@ -31,6 +36,8 @@ import torch.distributed as dist  # noqa: E402
 
 MFMA_PEAK_TF = {'bf16': 2500.0, 'f32': 157.3}      # MI355X_MICROARCH.md, dense
 L1_W, SILOG_W, SILOG_LAMBDA, LR = 0.237, 0.637, 0.869, 0.002   # conf/mode/train.yaml
+DUMP_MAX_ELEMS = 8 << 20        # 32 MiB of float32: a larger prediction is dumped as a fixed, seeded sample
+DUMP_PARAM_SAMPLE = 4 << 20     # 16 MiB of float32 of the updated parameters
 
 
 def synth_batch(B, S, seed, device):
@@ -40,6 +47,30 @@ def synth_batch(B, S, seed, device):
     gt = 30.0 * torch.rand(B, 1, S, S, generator=g)
     gt[gt < 3.0] = 0.0
     return audio.to(device), gt.to(device)
+
+
+def seeded_sample(x, n, seed):
+    """``x`` flattened, or its values at ``n`` fixed pseudo-random positions (seeded) when it holds more."""
+    x = x.detach().float().reshape(-1)
+    if x.numel() <= n:
+        return x.cpu().numpy()
+    idx = torch.randint(0, x.numel(), (n,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return x[idx.to(x.device)].cpu().numpy()
+
+
+def dump_outputs(out_dir, loss, pred, params):
+    """What the caller of the timed step receives, as float32 .npy: loss.npy; the prediction, pred.npy (B x 1 x S x S),
+    or pred_sample.npy above DUMP_MAX_ELEMS values; and params_sample.npy, the model's parameters after the step at
+    DUMP_PARAM_SAMPLE fixed positions of their concatenation (all of unet_256 would be 218 MB)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'loss.npy'), loss.detach().float().reshape(1).cpu().numpy())
+    if pred.numel() <= DUMP_MAX_ELEMS:
+        np.save(os.path.join(out_dir, 'pred.npy'), pred.detach().float().cpu().numpy())
+    else:
+        np.save(os.path.join(out_dir, 'pred_sample.npy'), seeded_sample(pred, DUMP_MAX_ELEMS, 0))
+    flat = torch.cat([p.detach().reshape(-1) for p in params])
+    np.save(os.path.join(out_dir, 'params_sample.npy'), seeded_sample(flat, DUMP_PARAM_SAMPLE, 1))
 
 
 def effective_cores():
@@ -182,6 +213,39 @@ def f32_exact_record(device, B, S, rank):
             'note': 'exact-f32 MFMA path (v_mfma_f32_16x16x4_f32): predictions within 1e-4 relative L1 of the CPU reference'}
 
 
+def roofline_record(fam, dtype, B, prof_steps):
+    """The dominant GEMM family of gemm_event_pass against the MFMA peak of ``dtype``."""
+    dom = max(fam, key=lambda k: fam[k][1])
+    flops, secs, launches = fam[dom]
+    achieved = flops / secs / 1e12
+    peak = MFMA_PEAK_TF[dtype]
+    gemm_secs = sum(v[1] for v in fam.values())
+    # HBM bytes per launch of the dominant kernel: NOT measured in this run -- taken from the committed PMC passes
+    # of this command (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate runs, read side doubled per
+    # MI355X_MICROARCH.md; tools/pmc_traffic.py); null when no such file matches
+    traffic, traffic_src, traffic_commit = None, None, None
+    for name in ('r03_pmc_traffic_gemm.json', 'r02_pmc_traffic_gemm.json', 'r01_pmc_traffic_gemm.json'):
+        try:
+            pm = json.load(open(os.path.join(ROOT, 'profiles', name)))
+            fams = (('igemm_ring_kernel', 'igemm_patch_kernel', 'igemm_mfma_kernel') if dom == 'igemm'
+                    else ('wgrad_k4_patch_kernel', 'wgrad_mfma_kernel'))
+            rows = [v for k, v in pm.items() if k.startswith(fams) and isinstance(v, dict)]
+            if rows and dtype == 'bf16' and B == 32:
+                traffic = sum(r['launches'] * r['hbm_bytes_per_launch'] for r in rows) / sum(r['launches'] for r in rows)
+                traffic_src, traffic_commit = 'profiles/' + name, pm.get('_commit')
+                break
+        except Exception:
+            continue
+    return {'bound': 'mfma',
+            'kernel': {'igemm': 'igemm_ring_kernel + igemm_patch_kernel + igemm_mfma_kernel (implicit-GEMM family: forward + input gradients)',
+                       'wgrad': 'wgrad_k4_patch_kernel + wgrad_mfma_kernel (weight gradients)'}.get(dom, dom),
+            'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s', 'frac': achieved / peak,
+            'traffic': traffic, 'traffic_source': traffic_src, 'traffic_commit': traffic_commit, 'launches': launches,
+            'avg_launch_ms': 1e3 * secs / launches,
+            'gemm_ms_per_step': 1e3 * gemm_secs / max(1, prof_steps),
+            'all_gemm_tflops': sum(v[0] for v in fam.values()) / gemm_secs / 1e12}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -189,17 +253,23 @@ def main():
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--batch', type=int, default=32, help='per-GPU batch')
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the loss, prediction and updated parameters (sampled) of the last timed step to DIR/*.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure roofline, sustained, f32_exact and cpu_baseline (off: the headline only)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip cpu_baseline')
     ap.add_argument('--no-graph', action='store_true', help='launch every kernel eagerly (default for --gpus > 1)')
-    ap.add_argument('--no-f32', action='store_true', help='skip the exact-f32 sub-record (N=1 only)')
+    ap.add_argument('--no-f32', action='store_true', help='with --full: skip the exact-f32 sub-record (N=1 only)')
     ap.add_argument('--sustain-seconds', type=float, default=2.0,
-                    help='length of the sustained per-step-event run behind the timed region (0 = skip)')
+                    help='with --full: length of the sustained per-step-event run behind the timed region (0 = skip)')
     ap.add_argument('--ddp-payload', default='f32', choices=['f32', 'bf16'],
                     help='what the gradient all-reduce carries (N > 1): f32 = DataParallel arithmetic (default), bf16 = half the bytes')
     ap.add_argument('--bucket-mb', type=int, default=32, help='all-reduce bucket size (N > 1)')
     ap.add_argument('--cpu-batch', type=int, default=8)
     ap.add_argument('--cpu-steps', type=int, default=25)     # B=8: about 12 s of host work (bounded sample)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     from audio_depth_estimation_amd import ddp as addp
 
@@ -234,7 +304,11 @@ def main():
     trainer.step(*batches[0])
     barrier()
     prof_steps = max(1, min(args.steps, 5))
-    fam = gemm_event_pass(trainer, batches, prof_steps)
+    if args.full:
+        fam = gemm_event_pass(trainer, batches, prof_steps)
+    else:       # the same steps without the event pairs: the timed region starts from the same state either way
+        for it in range(prof_steps):
+            trainer.step(*batches[it % len(batches)])
     barrier()
     if use_graph:
         trainer._plan, trainer._plan_after = None, None
@@ -244,7 +318,7 @@ def main():
     # ---- the timed region of the contract: exactly K steps between two barrier + synchronize pairs
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss, _ = trainer.step(*batches[i % len(batches)])
+        loss, pred = trainer.step(*batches[i % len(batches)])
     barrier()
     elapsed = time.perf_counter() - t0
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
@@ -252,9 +326,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:      # before anything else steps the trainer (its outputs are reused buffers)
+        dump_outputs(args.dump_outputs, loss, pred, list(model.parameters()))
     # ---- sustained run behind it: >= 2 s of back-to-back steps, one event per step, median reported
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         n_sust = max(50, min(4000, int(args.sustain_seconds / (elapsed / args.steps)) + 1))    # same on every rank
         times, wall = per_step_times(trainer, batches, n_sust)
         barrier()
@@ -265,27 +341,6 @@ def main():
                      'value_at_median': world * B / (med * 1e-3)}
 
     if rank == 0:
-        dom = max(fam, key=lambda k: fam[k][1])
-        flops, secs, launches = fam[dom]
-        achieved = flops / secs / 1e12
-        peak = MFMA_PEAK_TF[args.dtype]
-        gemm_secs = sum(v[1] for v in fam.values())
-        # HBM bytes per launch of the dominant kernel: NOT measured in this run -- taken from the committed PMC passes
-        # of this command (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate runs, read side doubled per
-        # MI355X_MICROARCH.md; tools/pmc_traffic.py); null when no such file matches
-        traffic, traffic_src, traffic_commit = None, None, None
-        for name in ('r03_pmc_traffic_gemm.json', 'r02_pmc_traffic_gemm.json', 'r01_pmc_traffic_gemm.json'):
-            try:
-                pm = json.load(open(os.path.join(ROOT, 'profiles', name)))
-                fams = (('igemm_ring_kernel', 'igemm_patch_kernel', 'igemm_mfma_kernel') if dom == 'igemm'
-                        else ('wgrad_k4_patch_kernel', 'wgrad_mfma_kernel'))
-                rows = [v for k, v in pm.items() if k.startswith(fams) and isinstance(v, dict)]
-                if rows and args.dtype == 'bf16' and B == 32:
-                    traffic = sum(r['launches'] * r['hbm_bytes_per_launch'] for r in rows) / sum(r['launches'] for r in rows)
-                    traffic_src, traffic_commit = 'profiles/' + name, pm.get('_commit')
-                    break
-            except Exception:
-                continue
         par = f'dp{world}'
         if world > 1:
             par += (f' ({"RCCL" if backend == "nccl" else backend} gradient all-reduce in {args.bucket_mb} MiB buckets beside '
@@ -299,22 +354,16 @@ def main():
                                    f'batch {B}/GPU, Combined L1+SIlog loss, clip 1.0, AdamW',
                        'global_batch': world * B, 'image_size': S, 'launch': 'hipGraph' if use_graph else 'launch-plan',
                        'parallelism': par},
-            'roofline': {'bound': 'mfma',
-                         'kernel': {'igemm': 'igemm_ring_kernel + igemm_patch_kernel + igemm_mfma_kernel (implicit-GEMM family: forward + input gradients)',
-                                    'wgrad': 'wgrad_k4_patch_kernel + wgrad_mfma_kernel (weight gradients)'}.get(dom, dom),
-                         'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s', 'frac': achieved / peak,
-                         'traffic': traffic, 'traffic_source': traffic_src, 'traffic_commit': traffic_commit, 'launches': launches,
-                         'avg_launch_ms': 1e3 * secs / launches,
-                         'gemm_ms_per_step': 1e3 * gemm_secs / max(1, prof_steps),
-                         'all_gemm_tflops': sum(v[0] for v in fam.values()) / gemm_secs / 1e12},
-            'sustained': sustained,
-            'final_loss': final_loss,
         }
-        if world == 1 and not args.no_f32 and args.dtype == 'bf16':
+        if args.full:
+            result['roofline'] = roofline_record(fam, args.dtype, B, prof_steps)
+            result['sustained'] = sustained
+        result['final_loss'] = final_loss
+        if args.full and world == 1 and not args.no_f32 and args.dtype == 'bf16':
             del trainer, model
             torch.cuda.empty_cache()
             result['f32_exact'] = f32_exact_record(device, B, S, rank)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result['cpu_baseline'] = cpu_baseline(args.cpu_batch, args.cpu_steps, 2)
         print(json.dumps(result), flush=True)
     if world > 1:
