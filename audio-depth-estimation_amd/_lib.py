@@ -226,6 +226,13 @@ _PROTOS = {
     'adn_resize_bilinear': (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     'adn_resize_bilinear_bwd': (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     'adn_clamp_range': (C.c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p]),
+    'adn_vae_fwd': (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, C.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_int32, c_void_p, c_void_p]),
+    'adn_vae_bwd_workspace_bytes': (c_int64, [c_int32, c_int32]),
+    'adn_vae_bwd': (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 _lib = None

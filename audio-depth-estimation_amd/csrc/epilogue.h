@@ -3,8 +3,9 @@
 #pragma once
 #include "adn_common.h"
 
+// kind 0 ReLU, 1 Sigmoid, 2 identity (the cVAE head with depth_norm)
 __device__ __forceinline__ float adn_final_act(float y, int kind) {
-  return kind == 1 ? 1.0f / (1.0f + __expf(-y)) : fmaxf(y, 0.0f);
+  return kind == 1 ? 1.0f / (1.0f + __expf(-y)) : (kind == 2 ? y : fmaxf(y, 0.0f));
 }
 
 // ---- scalar form ---------------------------------------------------------------------------------

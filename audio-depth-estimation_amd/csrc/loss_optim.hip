@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const double* partial
   }
 }
 
-// final_act >= 0 (0 ReLU, 1 Sigmoid; pred is the activation's OUTPUT): grad receives d loss / d pre-activation
+// final_act >= 0 (0 ReLU, 1 Sigmoid, 2 identity; pred is the activation's OUTPUT): grad receives d loss / d pre-activation
 // = d loss / d pred * act'(pred) -- what adn_final_act_bwd would make of it -- and bias_partials[block] its partial sum
 // (the gradient of the last layer's bias: sum over all pixels), so neither needs a pass of its own.
 __global__ __launch_bounds__(256) void loss_finish_kernel(const float* pred, const float* gt, int64_t n, float scale,
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(const float* pred, con
       }
     }
     if (final_act >= 0) {
-      gr *= final_act == 1 ? o * (1.0f - o) : (o > 0.f ? 1.0f : 0.0f);      // as final_act_bwd_kernel
+      gr *= final_act == 1 ? o * (1.0f - o) : (final_act == 2 ? 1.0f : (o > 0.f ? 1.0f : 0.0f));   // as final_act_bwd_kernel
       bsum += (double)gr;
     }
     grad[i] = gr;
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256) void final_act_bwd_kernel(const float* gout, c
                                                             int cpad, T* dz) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const float o = out[i];
-    const float d = kind == 1 ? o * (1.0f - o) : (o > 0.f ? 1.0f : 0.0f);
+    const float d = kind == 1 ? o * (1.0f - o) : (kind == 2 ? 1.0f : (o > 0.f ? 1.0f : 0.0f));
     ElemTraits<T>::store(dz + i * cpad, gout[i] * d);
     for (int c = 1; c < cpad; ++c) ElemTraits<T>::store(dz + i * cpad + c, 0.0f);
   }
@@ -349,7 +349,8 @@ extern "C" int adn_loss_finish_dz(const float* pred, const float* gt, int64_t n,
   ADN_CHECK_ARG(pred && gt && n > 0 && stats && dz && workspace, "adn_loss_finish_dz: bad arguments");
   ADN_CHECK_ARG(criterion >= 0 && criterion <= 2, "adn_loss_finish_dz: criterion %d (0 L1, 1 SIlog, 2 Combined)", criterion);
   ADN_CHECK_ARG(mask_mode >= 0 && mask_mode <= 2, "adn_loss_finish_dz: bad mask_mode %d", mask_mode);
-  ADN_CHECK_ARG(final_act == 0 || final_act == 1, "adn_loss_finish_dz: final_act %d (0 ReLU, 1 Sigmoid)", final_act);
+  ADN_CHECK_ARG(final_act >= 0 && final_act <= 2, "adn_loss_finish_dz: final_act %d (0 ReLU, 1 Sigmoid, 2 identity)",
+                final_act);
   int64_t nb = adn_cdiv(n, 256);
   if (nb > 4096) nb = 4096;
   ADN_CHECK_ARG(workspace_bytes >= nb * 8, "adn_loss_finish_dz: workspace too small");

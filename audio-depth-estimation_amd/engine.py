@@ -26,7 +26,7 @@ import torch
 from . import _lib
 from . import kernels as K
 from .flat import FlatParamEngine
-from ._lib import EPI_ACT, EPI_BWD, EPI_FINAL, EPI_Z_STATS, GEMM_S2, GEMM_T2
+from ._lib import EPI_ACT, EPI_BWD, EPI_FINAL, EPI_RAW, EPI_Z_STATS, GEMM_S2, GEMM_T2
 
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
@@ -44,6 +44,8 @@ class UNetEngine(FlatParamEngine):
         self.levels = module._adn_levels()          # list of dicts with layer objects, outermost first
         assert len(self.levels) == num_downs
         self.model_name = 'UnetGenerator'
+        self.final_act = 1 if self.depth_norm else 0      # head: 0 ReLU, 1 Sigmoid, 2 identity (cVAE)
+        self.vae = None                                    # cVAE bottleneck (CVAEEngine); None: the plain U-Net
         self._init_flat()
         self._saved = None
 
@@ -125,7 +127,7 @@ class UNetEngine(FlatParamEngine):
             lv.update(down_ypad=cd_in_p, up_ypad=cu_out_p)
             act = lambda c, h=hs, w_=wsz: torch.empty(B, h, w_, c, dtype=T, device=dev)
             lv['ad'] = act(cd_out) if i < n - 1 else None
-            lv['rd'] = act(cd_out)
+            lv['rd'] = None if self._no_skip(i) else act(cd_out)
             lv['Gd'] = act(cd_out)
             lv['zd'] = act(cd_out) if lv['bn_d'] is not None else None
             big = lambda c, h=hs, w_=wsz: torch.empty(B, 2 * h, 2 * w_, c, dtype=T, device=dev)
@@ -147,8 +149,9 @@ class UNetEngine(FlatParamEngine):
             c_up0 = cd_out
             c_up1 = cu_in - cd_out
             edge0 = i == 0 and self.edge_path
+            epi_d = EPI_RAW if self._vae_level(i) else (EPI_Z_STATS if lv['bn_d'] is not None else EPI_ACT)
             pd, w1 = (0, 0) if edge0 else K.igemm_query(T, GEMM_S2, B, hs, wsz, cd_in_p, 0, cd_out, [cd_out],   # Li fwd
-                                                       epi=EPI_Z_STATS if lv['bn_d'] is not None else EPI_ACT)
+                                                       epi=epi_d)
             if i == 0 and self.n1_path:
                 pu, w2 = 0, K.convt_n1_workspace_bytes(B, hs, wsz)                                  # D0 fwd
             else:
@@ -226,6 +229,8 @@ class UNetEngine(FlatParamEngine):
             if idx:
                 ws_bytes = max(ws_bytes, K.wgrad_patch_batch_workspace_bytes(T, B, [self.pshape[(tag, i)] for i in idx]))
         self._prepare_fused_norm(B, dev)
+        if self.vae is not None:
+            self._prepare_vae(B, dev)
         self.t2_table = torch.tensor(rows, dtype=torch.int64, device=dev)
         self.t2_layers, self.t2_blocks = len(rows), blk
         self.workspace = torch.empty(ws_bytes // 4 + 4, **f32)
@@ -233,6 +238,22 @@ class UNetEngine(FlatParamEngine):
         self.weights_dirty = True
         self._shape_key = key
         self.B = B
+
+    # ------------------------------------------------------------------ topology hooks (cVAE: CVAEEngine)
+    def _vae_level(self, i):
+        """Level whose down conv feeds the VAE bottleneck (raw f32 output, no activation)."""
+        return self.vae is not None and i == self.n - 1
+
+    def _no_skip(self, i):
+        """Level without a skip operand: the one directly above the cVAE bottleneck."""
+        return self.vae is not None and i == self.n - 2
+
+    def _up_inputs(self, i):
+        """Operands of level i's transposed conv: the skip rd[i] and the level below's ru[i+1] (a virtual concat)."""
+        L = self.levels
+        if self._no_skip(i):
+            return L[i + 1]['ru'], None
+        return L[i]['rd'], (L[i + 1]['ru'] if i < self.n - 1 else None)
 
     # ------------------------------------------------------------------ fused gradient norm
     supports_fused_norm = True
@@ -296,7 +317,10 @@ class UNetEngine(FlatParamEngine):
             src = self.x_nhwc if i == 0 else L[i - 1]['ad']
             C, hs, wsz = lv['cd_out'], lv['hs'], lv['ws']
             bn = lv['bn_d']
-            if i == 0 and self.edge_path:
+            if self._vae_level(i):
+                K.igemm(T, GEMM_S2, B, hs, wsz, src, None, lv['down_s2'], C, EPI_RAW, [K.Seg(C, out0=self.vae_h)], ws)
+                self._vae_forward(training)
+            elif i == 0 and self.edge_path:
                 K.l0_forward(x, self._flat_slice(self.flat_p, lv['down'].weight), B, hs, wsz, LEAKY, lv['ad'], lv['rd'])
             elif bn is None:
                 K.igemm(T, GEMM_S2, B, hs, wsz, src, None, lv['down_s2'], C, EPI_ACT,
@@ -314,13 +338,12 @@ class UNetEngine(FlatParamEngine):
         # ---- up path
         for i in reversed(range(n)):
             lv = L[i]
-            in0 = lv['rd']
-            in1 = L[i + 1]['ru'] if i < n - 1 else None
+            in0, in1 = self._up_inputs(i)
             C, hs, wsz = lv['cu_out'], lv['hs'], lv['ws']
             bn = lv['bn_u']
             if i == 0:
                 bias = lv['up'].bias
-                fa = 1 if self.depth_norm else 0
+                fa = self.final_act
                 if self.n1_path:
                     K.convt_n1_forward(T, B, hs, wsz, in0, in1, self._flat_slice(self.flat_p, lv['up'].weight), bias,
                                        fa, lv['out'], ws)
@@ -388,7 +411,7 @@ class UNetEngine(FlatParamEngine):
         if not getattr(self, 'edge_path', False) or l0.get('cu_out') != 1 or os.environ.get('ADN_NO_FUSED_DZ'):
             return None
         bias = l0['up'].bias
-        return l0['dz0'], (None if bias is None else self._flat_slice(self.flat_g, bias)), 1 if self.depth_norm else 0
+        return l0['dz0'], (None if bias is None else self._flat_slice(self.flat_g, bias)), self.final_act
 
     def backward(self, gout, fused_norm=False, dz_ready=False):
         """gout: d loss / d output, f32 [B, Cout, H, W].  Fills flat_g (all parameters); with ``fused_norm`` also
@@ -402,7 +425,7 @@ class UNetEngine(FlatParamEngine):
         up0 = l0['up']
         if not dz_ready:
             gout = gout.contiguous().float()
-            K.final_act_bwd(gout, l0['out'], 1 if self.depth_norm else 0, l0['dz0'])
+            K.final_act_bwd(gout, l0['out'], self.final_act, l0['dz0'])
             if up0.bias is not None:
                 K.sum_to_scalar(l0['dz0'], self._flat_slice(self.flat_g, up0.bias), self.red_ws)
         # ---- up layers, outermost first
@@ -427,9 +450,8 @@ class UNetEngine(FlatParamEngine):
             else:
                 self._bn_backward(lv, 'u', lv['bn_u'], B * 4 * hs * wsz, L[i - 1]['P_gu'], lv['Gu'], lv['zu'])
                 dz = lv['Gu']
-            in0 = lv['rd']
-            in1 = L[i + 1]['ru'] if i < n - 1 else None
-            segs = [K.Seg(lv['cd_out'], out0=lv['Gd'], ref=lv['rd'], slope=0.0)]
+            in0, in1 = self._up_inputs(i)
+            segs = [] if lv['rd'] is None else [K.Seg(lv['cd_out'], out0=lv['Gd'], ref=lv['rd'], slope=0.0)]
             if i < n - 1:
                 nx = L[i + 1]
                 segs.append(K.Seg(nx['cu_out'], out0=nx['Gu'], ref=nx['ru'], slope=0.0, z=nx['zu'],
@@ -461,6 +483,8 @@ class UNetEngine(FlatParamEngine):
                 self._ready(lv['up'].weight)
             K.igemm(T, GEMM_S2, B, hs, wsz, dz, None, lv['up_s2'], lv['cu_in'], EPI_BWD, segs, ws,
                     algo_c=lv['cu_out'])
+        if self.vae is not None:
+            self._vae_backward()                          # Gd[n-1]: d h_recon -> d h
         # ---- down layers, innermost first
         for i in reversed(range(n)):
             lv = L[i]
@@ -495,9 +519,10 @@ class UNetEngine(FlatParamEngine):
                 self._ready(lv['down'].weight)
             if i > 0:
                 pv = L[i - 1]
-                seg = K.Seg(pv['cd_out'], out0=pv['Gd'], ref=pv['ad'], slope=LEAKY, accumulate=True)
+                acc = pv['rd'] is not None                # no skip above the cVAE bottleneck: the only writer of Gd
+                seg = K.Seg(pv['cd_out'], out0=pv['Gd'], ref=pv['ad'], slope=LEAKY, accumulate=acc)
                 if pv['bn_d'] is not None:
-                    seg = K.Seg(pv['cd_out'], out0=pv['Gd'], ref=pv['ad'], slope=LEAKY, accumulate=True,
+                    seg = K.Seg(pv['cd_out'], out0=pv['Gd'], ref=pv['ad'], slope=LEAKY, accumulate=acc,
                                 z=pv['zd'], mean=pv['mean_d'], istd=pv['istd_d'], partials=pv['bpart_d'],
                                 scale=pv['scale_d'], shift=pv['shift_d'])
                 K.igemm(T, GEMM_T2, B, hs, wsz, lv['Gd'], None, lv['down_t2'], lv['cd_in'], EPI_BWD, [seg], ws)

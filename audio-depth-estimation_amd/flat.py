@@ -41,7 +41,8 @@ class FlatParamEngine:
     _SHAPE_INDEPENDENT = frozenset((
         'module', 'dtype', 'requested_dtype', 'mx8', 'model_name', 'depth_norm', 'n', 'levels', '_build', '_saved', 'flat_p', 'flat_g', 'flat_w16',
         'param_meta', 'total', 'offset', 'on_grad_ready', '_shape_key', '_shape_sets', '_packed_version',
-        'weights_dirty', 's2_fresh', 'train_offset', 'step_counter', 'dropout_seed'))
+        'weights_dirty', 's2_fresh', 'train_offset', 'step_counter', 'dropout_seed', 'final_act', 'vae', 'vae_seed',
+        'vae_draws', 'eps_in', 'g_kl', 'loss_acc', 'unused_params'))
     MAX_SHAPE_SETS = 4
 
     def _shape_snapshot(self):
@@ -93,9 +94,13 @@ class FlatParamEngine:
         base = self.flat_p.data_ptr()
         return p0.data_ptr() == base + 4 * off0 and pl.data_ptr() == base + 4 * offl
 
+    def _flat_params(self):
+        """The parameters the flat buffers hold, in parameters() order (an engine may leave out ones it never uses)."""
+        return list(self.module.parameters())
+
     def bind_parameters(self):
         """(Re)create the flat parameter/gradient buffers and re-point the module's Parameters into them."""
-        params = list(self.module.parameters())
+        params = self._flat_params()
         dev = params[0].device
         if dev.type != 'cuda':
             raise RuntimeError(f'{self.model_name} runs on libadn HIP kernels only: move the model to a HIP device '

@@ -17,7 +17,8 @@ from ._lib import (ADN_BF16, ADN_F32, EPI_ACT, EPI_ADD, EPI_BWD, EPI_FINAL, EPI_
 __all__ = ['dtype_code', 'Seg', 'igemm', 'igemm_query', 'wgrad', 'wgrad_workspace_bytes', 'pack_weights',
            'nchw_to_nhwc', 'nhwc_to_nchw', 'bn_fwd_finalize', 'bn_eval_affine', 'bn_act', 'bn_bwd_finalize',
            'bn_bwd_apply', 'loss_stats', 'loss_finish', 'final_act_bwd', 'sum_to_scalar', 'grad_norm', 'grad_norm_ranges', 'wgrad_sq_count',
-           'optimizer_step', 'compute_errors', 'frontend', 'convt_n1_forward', 'convt_n1_workspace_bytes']
+           'optimizer_step', 'compute_errors', 'frontend', 'convt_n1_forward', 'convt_n1_workspace_bytes', 'vae_fwd',
+           'vae_bwd', 'vae_bwd_workspace_bytes']
 
 
 def _stream():
@@ -824,6 +825,62 @@ def dropout_mask(mask, p, seed, counter=None):
     _dev(mask, counter)
     _lib.call('adn_dropout_mask', ptr(mask), mask.numel(), float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(counter),
               _stream())
+
+
+def _vae_shapes(who, B, Cc, L, **named):
+    """Every operand of the VAE kernels must hold exactly its [rows, cols] (contiguous): the kernels index by B, C, L."""
+    for name, (t, numel) in named.items():
+        if t is None:
+            continue
+        short = t.numel() < numel if name == 'counter' else t.numel() != numel      # counter: reads element 0
+        if short or not t.is_contiguous():
+            raise RuntimeError(f'{who}: {name} has shape {tuple(t.shape)} (contiguous: {t.is_contiguous()}), expected '
+                               f'{numel} contiguous elements for B={B}, C={Cc}, L={L}')
+        if name in ('out_relu', 'g_rec', 'dh'):
+            dtype_code(t.dtype)
+        elif name == 'counter':
+            if t.dtype != torch.float64:
+                raise RuntimeError(f'{who}: counter must be float64')
+        elif t.dtype != torch.float32:
+            raise RuntimeError(f'{who}: {name} must be float32, got {t.dtype}')
+
+
+def vae_fwd(h, w_mu, b_mu, w_lv, b_lv, w_dec, b_dec, seed, counter, eps_in, mu, logvar, eps, z, kl_img, kl, out_relu):
+    """VAE bottleneck forward (adn_vae_fwd): h f32 [B, C]; weights f32 in nn.Linear layout; out_relu [B, C] in the
+    compute dtype (bf16 or f32) receives ReLU(fc_dec(z)).  eps_in (f32 [B, L]) replaces the in-kernel draw when given."""
+    B, Cc = h.shape[0], h.numel() // h.shape[0]
+    L = mu.shape[-1]
+    _vae_shapes('vae_fwd', B, Cc, L, h=(h, B * Cc), w_mu=(w_mu, L * Cc), b_mu=(b_mu, L), w_lv=(w_lv, L * Cc),
+                b_lv=(b_lv, L), w_dec=(w_dec, Cc * L), b_dec=(b_dec, Cc), counter=(counter, 1), eps_in=(eps_in, B * L),
+                mu=(mu, B * L), logvar=(logvar, B * L), eps=(eps, B * L), z=(z, B * L), kl_img=(kl_img, B), kl=(kl, 1),
+                out_relu=(out_relu, B * Cc))
+    _dev(h, w_mu, b_mu, w_lv, b_lv, w_dec, b_dec, counter, eps_in, mu, logvar, eps, z, kl_img, kl, out_relu)
+    _lib.call('adn_vae_fwd', ptr(h), B, Cc, L, ptr(w_mu), ptr(b_mu), ptr(w_lv), ptr(b_lv), ptr(w_dec), ptr(b_dec),
+              int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(counter), ptr(eps_in), ptr(mu), ptr(logvar), ptr(eps), ptr(z), ptr(kl_img),
+              ptr(kl), dtype_code(out_relu.dtype), ptr(out_relu), _stream())
+
+
+def vae_bwd_workspace_bytes(B, L):
+    return _lib.load().adn_vae_bwd_workspace_bytes(B, L)
+
+
+def vae_bwd(g_rec, h, mu, logvar, eps, z, w_mu, w_lv, w_dec, g_kl, dw_mu, db_mu, dw_lv, db_lv, dw_dec, db_dec, dh,
+            workspace, kl=None, loss=None):
+    """VAE bottleneck backward (adn_vae_bwd): g_rec [B, C] (compute dtype) = d loss / d h_recon after the ReLU mask;
+    g_kl device f32 [1]; dh [B, C] (compute dtype, may be g_rec itself).  With ``loss``: loss[0] += g_kl * kl."""
+    B, Cc = h.shape[0], h.numel() // h.shape[0]
+    L = mu.shape[-1]
+    _vae_shapes('vae_bwd', B, Cc, L, g_rec=(g_rec, B * Cc), h=(h, B * Cc), mu=(mu, B * L), logvar=(logvar, B * L),
+                eps=(eps, B * L), z=(z, B * L), w_mu=(w_mu, L * Cc), w_lv=(w_lv, L * Cc), w_dec=(w_dec, Cc * L),
+                g_kl=(g_kl, 1), dw_mu=(dw_mu, L * Cc), db_mu=(db_mu, L), dw_lv=(dw_lv, L * Cc), db_lv=(db_lv, L),
+                dw_dec=(dw_dec, Cc * L), db_dec=(db_dec, Cc), dh=(dh, B * Cc), kl=(kl, 1), loss=(loss, 1))
+    if g_rec.dtype != dh.dtype:
+        raise RuntimeError('vae_bwd: g_rec and dh must share the compute dtype')
+    _dev(g_rec, h, mu, logvar, eps, z, w_mu, w_lv, w_dec, g_kl, dw_mu, db_mu, dw_lv, db_lv, dw_dec, db_dec, dh, workspace,
+         kl, loss)
+    _lib.call('adn_vae_bwd', ptr(g_rec), dtype_code(g_rec.dtype), B, Cc, L, ptr(h), ptr(mu), ptr(logvar), ptr(eps), ptr(z),
+              ptr(w_mu), ptr(w_lv), ptr(w_dec), ptr(g_kl), ptr(dw_mu), ptr(db_mu), ptr(dw_lv), ptr(db_lv), ptr(dw_dec),
+              ptr(db_dec), ptr(kl), ptr(loss), ptr(dh), ptr(workspace), _nbytes(workspace), _stream())
 
 
 def bcast_add(gx, dg, scale, accumulate):

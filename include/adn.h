@@ -54,7 +54,7 @@ enum {
                         out1 = relu(y) if out1   (layers without BN, eval-mode BN)               */
   ADN_EPI_BWD,       /* g = v * (ref>0 ? 1 : slope) (+ out0 if accumulate); out0 = g;
                         optional partial sums of g and g*xhat, xhat=(z-mean)*istd                */
-  ADN_EPI_FINAL,     /* out0(f32) = final_act(v + bias[n]); final_act: 0 relu, 1 sigmoid         */
+  ADN_EPI_FINAL,     /* out0(f32) = final_act(v + bias[n]); final_act: 0 relu, 1 sigmoid, 2 id  */
   ADN_EPI_ADD        /* out0 (dtype) = (v + bias[n]) * scale[n] (+ ref) (+ out0 if accumulate); bias/scale/ref
                         optional; final_act != 0: scale is ONE device scalar (residual gate gamma).
                         Plain input-gradient accumulation, linear 1x1 projections, x + gamma * proj(att)   */
@@ -466,14 +466,14 @@ int adn_loss_finish(const float* pred, const float* gt, int64_t n, float scale, 
                     float silog_weight, float silog_lambda, float* loss_out, float* grad,
                     void* stream);
 /* adn_loss_finish for a 1-channel prediction that is the OUTPUT of the generator's last activation (final_act 0 ReLU,
- * 1 Sigmoid; train.py:656-674 through unetbaseline_model.py:201-206): dz (f32, n) = d loss / d pred * act'(pred), i.e. what
+ * 1 Sigmoid, 2 identity -- the cVAE head with depth_norm; train.py:656-674 through unetbaseline_model.py:201-206): dz (f32, n) = d loss / d pred * act'(pred), i.e. what
  * adn_final_act_bwd makes of adn_loss_finish's grad, and bias_grad (optional, f32 scalar) = sum(dz), the gradient of the last
  * layer's bias -- both without a pass of their own.  criterion 0-2.  workspace: min(4096, ceil(n / 256)) doubles. */
 int adn_loss_finish_dz(const float* pred, const float* gt, int64_t n, float scale, int32_t mask_mode, float eps,
                        const double* stats, int32_t criterion, float l1_weight, float silog_weight, float silog_lambda,
                        float* loss_out, float* dz, int32_t final_act, float* bias_grad, void* workspace,
                        int64_t workspace_bytes, void* stream);
-/* Derivative of the generator's last activation (ReLU or Sigmoid, unetbaseline_model.py:201-206):
+/* Derivative of the generator's last activation (0 ReLU, 1 Sigmoid, 2 identity; unetbaseline_model.py:201-206):
  * dz (dtype, [pixels][c_pad], channel 0 = gout * act'(out), other channels zero). */
 int adn_final_act_bwd(const float* gout, const float* out, int64_t n, int32_t final_act,
                       int32_t dtype, int32_t c_pad, void* dz, void* stream);
@@ -595,6 +595,31 @@ int adn_resize_bilinear(const float* src, int32_t planes, int32_t H, int32_t W, 
  * gout [planes][S][S] -> gin [planes][H][W], a gather per source pixel (deterministic, no atomics). */
 int adn_resize_bilinear_bwd(const float* gout, int32_t planes, int32_t H, int32_t W, int32_t S,
                             float* gin, void* stream);
+
+/* VAE bottleneck of the U-Net cVAE family (models/unet_cvae_model.py, VAEBottleneck on the 1x1 innermost level).
+ * Forward: h [B][C] f32 -> mu, logvar = Linear(C,L)(h) (weights [L][C], f32 masters); eps ~ N(0,1) drawn from a
+ * counter-based hash of (seed, counter, element) (Box-Muller; counter: optional device f64[1] step count mixed in ON
+ * THE DEVICE so a replayed hipGraph / launch plan draws fresh noise), or copied from eps_in [B][L] when non-NULL;
+ * z = mu + eps * exp(logvar / 2); out_relu [B][C] (dtype) = ReLU(Linear(L,C)(z)) (the innermost transposed conv's
+ * operand); kl_img [B] = -1/2 sum_j (1 + logvar - mu^2 - exp(logvar)); kl [1] = mean of kl_img in a fixed order.
+ * mu, logvar, eps, z: f32 [B][L], saved for the backward.  Two launches, no atomics, bit-reproducible.
+ * Needs B >= 1, C % 8 == 0, 1 <= L <= 1024 (ADN_ERR_ARG otherwise). */
+int adn_vae_fwd(const float* h, int32_t B, int32_t C, int32_t L, const float* w_mu, const float* b_mu,
+                const float* w_lv, const float* b_lv, const float* w_dec, const float* b_dec, uint64_t seed,
+                const double* counter, const float* eps_in, float* mu, float* logvar, float* eps, float* z,
+                float* kl_img, float* kl, int32_t dtype, void* out_relu, void* stream);
+/* Bytes of the adn_vae_bwd workspace (d mu and d logvar, f32 [2][B][L]); -1 for a bad shape. */
+int64_t adn_vae_bwd_workspace_bytes(int32_t B, int32_t L);
+/* Backward: g_rec [B][C] (dtype) = d loss / d h_recon, already ReLU-masked; g_kl = device f32[1] d loss / d kl.
+ * dmu = dz + g_kl mu / B, dlv = dz eps std / 2 + g_kl (exp(logvar) - 1) / (2B) with dz = W_dec^T g_rec;
+ * writes the three Linears' dW / db (overwritten, partitioned by output rows) and dh [B][C] (dtype) =
+ * W_mu^T dmu + W_lv^T dlv.  dh may alias g_rec (g_rec is consumed by the first of the two launches).
+ * loss (optional, device f32[1]): loss[0] += g_kl[0] * kl[0] (needs kl). */
+int adn_vae_bwd(const void* g_rec, int32_t dtype, int32_t B, int32_t C, int32_t L, const float* h, const float* mu,
+                const float* logvar, const float* eps, const float* z, const float* w_mu, const float* w_lv,
+                const float* w_dec, const float* g_kl, float* dw_mu, float* db_mu, float* dw_lv, float* db_lv,
+                float* dw_dec, float* db_dec, const float* kl, float* loss, void* dh, void* workspace,
+                int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
