@@ -1,6 +1,9 @@
-// Weight-gradient kernel of the k4/s2/p1 Conv2d / ConvTranspose2d pair (gfx950).
+// Tap-staged weight-gradient kernels of both conv geometries (gfx950) and the dispatch of every weight gradient:
+// the k4/s2/p1 Conv2d / ConvTranspose2d pair of the U-Net (geom 0) and the stride-1 3x3 / 1x1 convolutions of the
+// DoubleConv nets (ADN_GEMM_S1).  One kernel body serves both: the geometry is a template parameter, so the k4
+// instantiations fold kside = 4, kpad = 1, stride 2, 16 taps into their addressing.
 //
-//   dW[r][tap][c] = sum_{m on the small grid} plain[m][r] * gath[b, 2i-1+ky, 2j-1+kx][c]
+//   dW[r][tap][c] = sum_{m on the small grid} plain[m][r] * gath[b, g*i-kpad+ky, g*j-kpad+kx][c]      (g = 2 / 1)
 //
 // The contraction runs over PIXELS while both operands are channel-contiguous (NHWC), so the MFMA
 // fragments ("8 consecutive k per lane") are columns of the staged LDS tiles: the bf16 path reads
@@ -8,8 +11,10 @@
 // f32 path with ds_read_b32.  LDS tiles are [pixel][128 channels] with the 32-byte granule index
 // XOR-ed by f(row) = (row&3) | ((row>>3)&1)<<2, which makes both the transposed reads (8 rows x 32 B
 // per half-wave) conflict free; the tiles are filled by LDS-DMA with the swizzle on the source address.  Output tile 128(r) x 128(tap,c columns);
-// the pixel range is split over grid.z into f32 slabs that a second kernel sums (deterministic).
+// the pixel range is split over the grid into f32 slabs that a second kernel sums (deterministic).
+// The patch-staged kernels that take the large-image layers of both geometries live in wgrad_patch.hip.
 #include "adn_common.h"
+#include "wgrad_internal.h"
 
 namespace {
 
@@ -25,15 +30,27 @@ struct WParams {
   int c_valid;    // gathered channels actually stored (compact [R][taps][c_valid]); == C0+C1 normally
   int geom;       // 0: k4 s2 gather (16 taps, gathered tensor on the 2x grid); ADN_GEMM_S1: ks x ks, same grid
   int ks;
+  double* sq;     // optional (k4 only): per-workgroup sum of dW^2 (only with nsplit == 1 and c_valid == C: this kernel writes the final dW)
 };
+
+// sum over the 256 threads of a workgroup, result valid in thread 0 (sh: 4 doubles)
+__device__ __forceinline__ double wg_block_sum_d(double v, double* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
 
 // 128 zero bytes: LDS-DMA source for rows beyond M / padded taps / the upper half of an R=64 tile
 __device__ u32x4_t adn_wg_zero_page[8];
 
 __device__ __forceinline__ int swz_f(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
 
+// (the body is shared by the one-problem kernel and the multi-problem launch of the small-image layers: `bid` is the
+//  workgroup index inside its problem)
 template <typename T, bool FAST, bool MIXED, bool S1, bool HALF>
-__global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(WParams p) {
+__device__ __forceinline__ void wgrad_mfma_body(const WParams& p, const int bid) {
 #if defined(__HIP_DEVICE_COMPILE__)   // buffer-resource builtins exist only in the device pass
   constexpr int EPC = 16 / (int)sizeof(T);
   constexpr int BKP = sizeof(T) == 2 ? 64 : 32;       // pixels per step
@@ -56,8 +73,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(WParams p) {
   // operands through its L2 (blocks b and b+8 share an XCD)
   const int ntile = p.tiles_r * p.tiles_c;
   const int nblk = ntile * p.nsplit;
-  const int bq = nblk >> 3, br = nblk & 7, bx = blockIdx.x & 7;
-  const int lid = (bx < br ? bx * (bq + 1) : br * (bq + 1) + (bx - br) * bq) + (blockIdx.x >> 3);
+  const int bq = nblk >> 3, br = nblk & 7, bx = bid & 7;
+  const int lid = (bx < br ? bx * (bq + 1) : br * (bq + 1) + (bx - br) * bq) + (bid >> 3);
   const int tile_c = lid % p.tiles_c;
   const int tile_r = (lid / p.tiles_c) % p.tiles_r;
   const int split = lid / ntile;
@@ -200,7 +217,10 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(WParams p) {
       const int gsoff1 = gpix * p.C1 * ESZ;
 #pragma unroll
       for (int k = 0; k < PASSES; ++k) {
-        const bool inval = m_c[k] || (top && m_y0[k]) || (bot && m_y1[k]) || (left && m_x0[k]) || (right && m_x1[k]);
+        // k4: plain bit operations -- with the short-circuit form the compiler threads the scalar tests into copies of
+        // every request (12 more requests, ~250 instructions, 3-6 % slower k4 launches); S1 keeps the form it was tuned with
+        const bool inval = S1 ? (m_c[k] || (top && m_y0[k]) || (bot && m_y1[k]) || (left && m_x0[k]) || (right && m_x1[k]))
+                              : (m_c[k] | (top & m_y0[k]) | (bot & m_y1[k]) | (left & m_x0[k]) | (right & m_x1[k]));
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsp, (lptr_t)(pdst + k * (RPP * ROWB)), 16, pvoff[k], psoff, 0, 0);
         const unsigned gv = inval ? OOB : gvoff[k];
         if constexpr (MIXED) {
@@ -329,6 +349,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(WParams p) {
   if (p.c_valid == C) {
     const int64_t ldo = (int64_t)ntap * C;
     const bool cok = S1 ? (tile_c * 128 + cq * 4 < ntap * C) : true;
+    double sq = 0.0;
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
       const int row = r0 + 8 * k;
@@ -336,10 +357,19 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(WParams p) {
         f32x4_t v = *reinterpret_cast<const f32x4_t*>(ct + row * LDC + cq * 4);
         if (HALF) v += *reinterpret_cast<const f32x4_t*>(ct + (row + 64) * LDC + cq * 4);     // second pixel half
         *reinterpret_cast<f32x4_t*>(out + (int64_t)(tile_r * 128 + row) * ldo + tile_c * 128 + cq * 4) = v;
+        if constexpr (!S1) sq += (double)(v[0] * v[0] + v[1] * v[1]) + (double)(v[2] * v[2] + v[3] * v[3]);   // as sqsum_partial_kernel
+      }
+    }
+    // norm partials ride along only in the k4 kernels (fill_wparams leaves p.sq null for S1: compiled out there)
+    if constexpr (!S1) {
+      if (p.sq) {   // uniform: the final dW leaves this kernel, its share of the gradient norm rides along
+        __syncthreads();                              // everyone is done with the staged tile: reuse its first bytes
+        sq = wg_block_sum_d(sq, reinterpret_cast<double*>(smem));
+        if (tid == 0) p.sq[lid] = sq;
       }
     }
   } else {
-    // zero-padded gathered channels (edge layers): keep only c < c_valid, compact [R][16][c_valid]
+    // zero-padded gathered channels (edge layers): keep only c < c_valid, compact [R][taps][c_valid]
     for (int k = 0; k < 16; ++k) {
       const int row = r0 + 8 * k;
       if (tile_r * 128 + row >= R) continue;
@@ -348,11 +378,33 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(WParams p) {
         const int tp = gc / C, cc = gc - tp * C;
         if (tp < ntap && cc < p.c_valid)
           out[((int64_t)(tile_r * 128 + row) * ntap + tp) * p.c_valid + cc] =
-              ct[row * LDC + cq * 4 + e] + (HALF ? ct[(row + 64) * LDC + cq * 4 + e] : 0.f);
+              HALF ? ct[row * LDC + cq * 4 + e] + ct[(row + 64) * LDC + cq * 4 + e] : ct[row * LDC + cq * 4 + e];
       }
     }
   }
 #endif
+}
+
+template <typename T, bool FAST, bool MIXED, bool S1, bool HALF>
+__global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(WParams p) {
+  wgrad_mfma_body<T, FAST, MIXED, S1, HALF>(p, (int)blockIdx.x);
+}
+
+// Several independent weight-gradient problems in ONE launch (the small-image levels of the U-Net: six launches of
+// 256-512 short workgroups each, whose time is launch ramp and dW write latency, not arithmetic).  k4 geometry only.
+constexpr int kWgradBatchMax = 8;
+struct WBatch {
+  WParams p[kWgradBatchMax];
+  int first[kWgradBatchMax + 1];      // first workgroup of problem k; first[n] = grid size
+  int n;
+};
+template <typename T, bool FAST>
+__global__ __launch_bounds__(256, 2) void wgrad_mfma_batch_kernel(WBatch b) {
+  int k = 0;
+#pragma unroll
+  for (int j = 1; j < kWgradBatchMax; ++j)
+    if (j < b.n && (int)blockIdx.x >= b.first[j]) k = j;
+  wgrad_mfma_body<T, FAST, false, false, false>(b.p[k], (int)blockIdx.x - b.first[k]);
 }
 
 // generic path: one thread per (output element, split)
@@ -391,10 +443,11 @@ __global__ __launch_bounds__(256) void wgrad_direct_kernel(WParams p, int pix_pe
   p.out[(int64_t)split * p.out_elems + e] = acc;
 }
 
-__global__ __launch_bounds__(256) void slab_sum_kernel(const float* slab, float* out, int64_t n, int nsplit) {
-  // n is a multiple of 4 (R*16*c with R % 64 == 0); 4 independent accumulator chains hide the load latency
+__global__ __launch_bounds__(256) void slab_sum_kernel(const float* slab, float* out, int64_t n, int nsplit, double* sq) {
+  // n is a multiple of 4 (R*taps*c with R % 64 == 0); 4 independent accumulator chains hide the load latency
   const int64_t n4 = n >> 2;
   const f32x4_t* s4 = reinterpret_cast<const f32x4_t*>(slab);
+  double sqs = 0.0;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n4; e += (int64_t)gridDim.x * 256) {
     f32x4_t a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0;
     int s = 0;
@@ -405,52 +458,80 @@ __global__ __launch_bounds__(256) void slab_sum_kernel(const float* slab, float*
       a3 += s4[(int64_t)(s + 3) * n4 + e];
     }
     for (; s < nsplit; ++s) a0 += s4[(int64_t)s * n4 + e];
-    reinterpret_cast<f32x4_t*>(out)[e] = (a0 + a1) + (a2 + a3);
+    const f32x4_t v = (a0 + a1) + (a2 + a3);
+    reinterpret_cast<f32x4_t*>(out)[e] = v;
+    sqs += (double)(v[0] * v[0] + v[1] * v[1]) + (double)(v[2] * v[2] + v[3] * v[3]);      // as sqsum_partial_kernel
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
     const int64_t e = (n4 << 2) + threadIdx.x;
     float v = 0.f;
     for (int s = 0; s < nsplit; ++s) v += slab[(int64_t)s * n + e];
     out[e] = v;
+    sqs += (double)v * v;
   }
+  if (sq) {         // uniform: this launch writes the final dW, its share of the gradient norm rides along
+    __shared__ double sh[4];
+    sqs = wg_block_sum_d(sqs, sh);
+    if (threadIdx.x == 0) sq[blockIdx.x] = sqs;
+  }
+}
+
+// workgroups of the slab sum: enough to stream at the HBM rate; fewer when every workgroup leaves a norm partial behind
+inline int64_t slab_sum_blocks(int64_t out_elems, bool sq) {
+  int64_t blocks = adn_cdiv(adn_cdiv(out_elems, 4), 256);
+  const int64_t cap = sq ? 1024 : 4096;
+  return blocks > cap ? cap : blocks;
 }
 
 struct WPlan {
   bool mfma;
   bool fast;
-  bool mixed;    // fast path whose 128-column tiles straddle the two gathered sources
+  bool mixed;    // S1 only: fast path whose 128-column tiles straddle the two gathered sources
   int nsplit, steps, tiles_r, tiles_c, pix_per_split;
   int64_t out_elems, slab_bytes;
 };
 
+// Plan of the tap-staged kernels.  The two geometries follow different policies ON PURPOSE (they decide nsplit, hence the
+// summation order, hence the bits of dW): every difference is an explicit branch below, none is to be "unified".
 void make_wplan(const AdnWgradDesc* d, WPlan* pl) {
+  const bool s1 = d->geom == ADN_GEMM_S1;
   const int R = d->R0 + d->R1, C = d->C0 + d->C1;
   const int64_t msmall = (int64_t)d->B * d->Hs * d->Ws;
   const int cv = d->c_valid > 0 ? d->c_valid : C;
-  const int ntap = d->geom == ADN_GEMM_S1 ? d->ks * d->ks : 16;
+  const int ntap = s1 ? d->ks * d->ks : 16;
   pl->out_elems = (int64_t)R * ntap * cv;
   const int epc = d->dtype == ADN_BF16 ? 8 : 4;
   // sources are selected per 16-byte chunk, so a tile may straddle the two plain / gathered sources
-  // tap, channel and source are per-lane constants of a 16-byte chunk, so a 128-column tile may straddle taps
-  // (C = 192, 96, ...) as well as the two gathered sources; only chunks must not straddle anything
-  const bool aligned = (R % 64 == 0) && (d->R0 % epc == 0) && (C % epc == 0) && (d->C0 % epc == 0);
+  bool aligned = (R % 64 == 0) && (d->R0 % epc == 0) && (C % epc == 0) && (d->C0 % epc == 0);
+  // S1: tap, channel and source are per-lane constants of a 16-byte chunk, so a 128-column tile may straddle taps
+  // (C = 192, 96, ...) as well as the two gathered sources; only chunks must not straddle anything.
+  // k4 (stricter): whole column tiles, and a tile holds whole taps or a tap whole tiles -- everything else takes the
+  // direct kernel
+  if (!s1) aligned = aligned && ((16 * C) % 128 == 0) && (C >= 128 ? (C % 128 == 0) : (128 % C == 0));
   pl->mfma = aligned;
   pl->fast = false;
   pl->mixed = false;
   if (aligned) {
     const int bkp = d->dtype == ADN_BF16 ? 64 : 32;
-    const int64_t esz = d->dtype == ADN_BF16 ? 2 : 4;
+    const int maxC = d->C0 > d->C1 ? d->C0 : d->C1, maxR = d->R0 > d->R1 ? d->R0 : d->R1;
     auto pow2 = [](int x) { return x > 0 && (x & (x - 1)) == 0; };
-    pl->fast = pow2(d->Hs) && pow2(d->Ws) && d->Hs * d->Ws >= bkp && (d->R1 == 0 || d->R0 % 128 == 0) &&
-               msmall * (d->geom == ADN_GEMM_S1 ? 1 : 4) * (d->C0 > d->C1 ? d->C0 : d->C1) * esz < (1ll << 31) &&
-               msmall * (d->R0 > d->R1 ? d->R0 : d->R1) * esz < (1ll << 31);     // 32-bit scalar byte offsets
-    pl->mixed = pl->fast && d->C1 > 0 && (C % 128 != 0 || (d->C0 % 128) != 0);
+    pl->fast = pow2(d->Hs) && pow2(d->Ws) && d->Hs * d->Ws >= bkp && (d->R1 == 0 || d->R0 % 128 == 0);
+    if (s1) {
+      const int64_t esz = d->dtype == ADN_BF16 ? 2 : 4;
+      pl->fast = pl->fast && msmall * maxC * esz < (1ll << 31) && msmall * maxR * esz < (1ll << 31);   // 32-bit scalar byte offsets
+      pl->mixed = pl->fast && d->C1 > 0 && (C % 128 != 0 || (d->C0 % 128) != 0);
+    } else {
+      // no MIXED form: a two-source concat is fast only when every column tile lies inside one source; the offset test
+      // counts 4 bytes per element for both dtypes and the 2x grid of the gathered tensor
+      pl->fast = pl->fast && (d->C1 == 0 || (d->C0 % 128 == 0 && C % 128 == 0)) &&
+                 msmall * 4 * maxC * 4 < (1ll << 31) && msmall * maxR * 4 < (1ll << 31);
+    }
     pl->steps = (int)adn_cdiv(msmall, bkp);
     pl->tiles_r = (int)adn_cdiv(R, 128);
-    pl->tiles_c = (int)adn_cdiv((int64_t)ntap * C, 128);
+    pl->tiles_c = s1 ? (int)adn_cdiv((int64_t)ntap * C, 128) : 16 * C / 128;
     const int64_t tiles = (int64_t)pl->tiles_r * pl->tiles_c;
-    // one resident wave of workgroups: 256 CUs x 2 workgroups; never 513 (9 taps x 57 splits ran a 2x tail)
-    int ns = (int)(512 / tiles);
+    // one resident wave of workgroups: 256 CUs x 2 workgroups.  S1: never 513 (9 taps x 57 splits ran a 2x tail); k4 rounds up
+    int ns = s1 ? (int)(512 / tiles) : (int)adn_cdiv(512, tiles);
     const int max_by_steps = pl->steps / 4 > 0 ? pl->steps / 4 : 1;
     if (ns > max_by_steps) ns = max_by_steps;
     if (ns > 256) ns = 256;
@@ -483,9 +564,11 @@ int wvalidate(const AdnWgradDesc* d) {
   return ADN_OK;
 }
 
-template <typename T>
-int wrun(const AdnWgradDesc* d, const WPlan& pl, hipStream_t st) {
-  WParams p;
+// Norm partials ride along only in the k4 pair's kernels (the U-Net baseline: 54 M parameters, the gradient pass the
+// fusion saves is 40 us of a 2.9 ms step); the stride-1 kernels of the DoubleConv nets report 0 = "not fused".
+inline double* sq_of(const AdnWgradDesc* d) { return d->geom == ADN_GEMM_S1 ? nullptr : d->sq_partials; }
+
+void fill_wparams(const AdnWgradDesc* d, const WPlan& pl, WParams& p) {
   p.plain0 = d->plain0; p.plain1 = d->plain1; p.R0 = d->R0; p.R1 = d->R1;
   p.gath0 = d->gath0; p.gath1 = d->gath1; p.C0 = d->C0; p.C1 = d->C1;
   p.B = d->B; p.Hs = d->Hs; p.Ws = d->Ws; p.Msmall = d->B * d->Hs * d->Ws;
@@ -495,136 +578,212 @@ int wrun(const AdnWgradDesc* d, const WPlan& pl, hipStream_t st) {
   p.c_valid = d->c_valid > 0 ? d->c_valid : d->C0 + d->C1;
   p.geom = d->geom;
   p.ks = d->ks;
+  p.sq = (pl.mfma && pl.nsplit == 1 && p.c_valid == d->C0 + d->C1) ? sq_of(d) : nullptr;
+}
+
+// The second half of every split launch: `nsplit` slabs at `slab` -> dw in fixed order; with `sq` one norm partial per workgroup
+int slab_sum(const float* slab, float* dw, int64_t out_elems, int nsplit, double* sq, hipStream_t st) {
+  if (nsplit <= 1) return ADN_OK;
+  const int64_t blocks = slab_sum_blocks(out_elems, sq != nullptr);
+  hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, st, slab, dw, out_elems, nsplit, sq);
+  ADN_CHECK_LAUNCH();
+  return ADN_OK;
+}
+
+template <typename T>
+constexpr int wgrad_lds() {
+  constexpr int BKP = sizeof(T) == 2 ? 64 : 32;
+  constexpr int stage = 4 * BKP * 128 * (int)sizeof(T);
+  constexpr int epil = 128 * 132 * 4;
+  return stage > epil ? stage : epil;
+}
+
+template <typename T>
+int wrun(const AdnWgradDesc* d, const WPlan& pl, hipStream_t st) {
+  WParams p;
+  fill_wparams(d, pl, p);
   if (pl.mfma) {
-    constexpr int BKP = sizeof(T) == 2 ? 64 : 32;
-    constexpr int stage = 4 * BKP * 128 * (int)sizeof(T);
-    constexpr int epil = 128 * 132 * 4;
-    constexpr int lds = stage > epil ? stage : epil;
+    constexpr int lds = wgrad_lds<T>();
     const dim3 grid(pl.tiles_r * pl.tiles_c * pl.nsplit);
-    const bool s1 = d->geom == ADN_GEMM_S1;
     const bool half = (d->R0 + d->R1) == 64;
-#define ADN_WG_LAUNCH1(FAST_, MIXED_, S1_, HALF_)                                                                      \
+#define ADN_WG_LAUNCH(FAST_, MIXED_, S1_, HALF_)                                                               \
   do {                                                                                                         \
     ADN_SET_LDS_ONCE(lds, &wgrad_mfma_kernel<T, FAST_, MIXED_, S1_, HALF_>);                                   \
     hipLaunchKernelGGL((wgrad_mfma_kernel<T, FAST_, MIXED_, S1_, HALF_>), grid, dim3(256), lds, st, p);        \
   } while (0)
-#define ADN_WG_LAUNCH(FAST_, MIXED_, S1_)                  \
-  do {                                                     \
-    if (half) ADN_WG_LAUNCH1(FAST_, MIXED_, S1_, true);    \
-    else ADN_WG_LAUNCH1(FAST_, MIXED_, S1_, false);        \
+#define ADN_WG_LAUNCH_S1(FAST_, MIXED_)                  \
+  do {                                                   \
+    if (half) ADN_WG_LAUNCH(FAST_, MIXED_, true, true);  \
+    else ADN_WG_LAUNCH(FAST_, MIXED_, true, false);      \
   } while (0)
-    if (pl.fast && pl.mixed) {
-      if (s1) ADN_WG_LAUNCH(true, true, true);
-      else ADN_WG_LAUNCH(true, true, false);
+    // only what the plans can ask for is instantiated: k4 has neither the MIXED nor the HALF form
+    if (d->geom != ADN_GEMM_S1) {
+      if (pl.fast) ADN_WG_LAUNCH(true, false, false, false);
+      else ADN_WG_LAUNCH(false, false, false, false);
+    } else if (pl.fast && pl.mixed) {
+      ADN_WG_LAUNCH_S1(true, true);
     } else if (pl.fast) {
-      if (s1) ADN_WG_LAUNCH(true, false, true);
-      else ADN_WG_LAUNCH(true, false, false);
+      ADN_WG_LAUNCH_S1(true, false);
     } else {
-      if (s1) ADN_WG_LAUNCH(false, false, true);
-      else ADN_WG_LAUNCH(false, false, false);
+      ADN_WG_LAUNCH_S1(false, false);
     }
+#undef ADN_WG_LAUNCH_S1
 #undef ADN_WG_LAUNCH
-#undef ADN_WG_LAUNCH1
   } else {
     hipLaunchKernelGGL((wgrad_direct_kernel<T>), dim3((unsigned)adn_cdiv(pl.out_elems, 256), pl.nsplit), dim3(256),
                        0, st, p, pl.pix_per_split);
   }
   ADN_CHECK_LAUNCH();
-  if (pl.nsplit > 1) {
-    int64_t blocks = adn_cdiv(adn_cdiv(pl.out_elems, 4), 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, st,
-                       reinterpret_cast<const float*>(d->workspace), d->dw, pl.out_elems, pl.nsplit);
-    ADN_CHECK_LAUNCH();
+  return slab_sum(reinterpret_cast<const float*>(d->workspace), d->dw, pl.out_elems, pl.nsplit, sq_of(d), st);
+}
+
+// What adn_wgrad does with a valid descriptor: the patch-staged kernel of its geometry where that applies, else the
+// tap-staged plan (MFMA or direct kernel).  Either way nsplit f32 slabs of out_elems, summed by slab_sum when nsplit > 1.
+struct WRoute {
+  bool patch;
+  int nsplit;
+  int64_t out_elems;
+  WPlan pl;       // valid when !patch
+  int64_t slab_bytes() const { return nsplit > 1 ? (int64_t)nsplit * out_elems * 4 : 0; }
+};
+
+WRoute wroute(const AdnWgradDesc* d) {
+  WRoute r;
+  r.patch = adn_wgrad_patch_plan(d, &r.nsplit, &r.out_elems);
+  if (!r.patch) {
+    make_wplan(d, &r.pl);
+    r.nsplit = r.pl.nsplit;
+    r.out_elems = r.pl.out_elems;
   }
-  return ADN_OK;
+  return r;
+}
+
+// Patch-staged k4 layers as ONE launch with 1/n of the pixel splits each (n <= 4 layers): per problem the split count of a
+// lone launch divided by n.  Slab regions are laid out back to back in descs[0].workspace.
+bool patch_batch_plan(const AdnWgradDesc* descs, int n, int* ns, int64_t* oe, int64_t* off, int64_t* total) {
+  int64_t at = 0;
+  for (int k = 0; k < n; ++k) {
+    int lone;
+    if (wvalidate(descs + k) != ADN_OK || descs[k].geom != 0 || !adn_wgrad_patch_plan(descs + k, &lone, &oe[k])) return false;
+    ns[k] = lone / n > 1 ? lone / n : 1;
+    off[k] = at;
+    if (ns[k] > 1) at += (int64_t)ns[k] * oe[k] * 4;
+  }
+  *total = at;
+  return true;
 }
 
 }  // namespace
 
-int64_t adn_wgrad_k4_workspace_bytes(const AdnWgradDesc* d);   // wgrad_k4.hip
-int adn_wgrad_k4(const AdnWgradDesc* d, void* stream);
-bool adn_wgrad_s1p_plan(const AdnWgradDesc* d, int* nsplit, int64_t* out_elems);   // wgrad_s1p.hip (patch-staged 3 x 3)
-int adn_wgrad_s1p_launch(const AdnWgradDesc* d, int nsplit, int64_t out_elems, void* stream);
-
-int32_t adn_wgrad_k4_sq_count(const AdnWgradDesc* d);   // wgrad_k4.hip
-int32_t adn_wgrad_k4_batchable(const AdnWgradDesc* d);
-int32_t adn_wgrad_k4_batch_sq_count(const AdnWgradDesc* d);
-int64_t adn_wgrad_k4_patch_batch_workspace_bytes(const AdnWgradDesc* descs, int32_t n);
-int adn_wgrad_k4_patch_batch(const AdnWgradDesc* descs, int32_t n, void* stream);
-int adn_wgrad_k4_batch(const AdnWgradDesc* descs, int32_t n, void* stream);
-
-// Norm partials ride along only in the k4 pair's kernels (the U-Net baseline: 54 M parameters, the gradient pass the
-// fusion saves is 40 us of a 2.9 ms step); the stride-1 kernels of the DoubleConv nets report 0 = "not fused".
-extern "C" int32_t adn_wgrad_sq_count(const AdnWgradDesc* d) {
-  if (!d || d->geom == ADN_GEMM_S1) return 0;
-  return adn_wgrad_k4_sq_count(d);
-}
-
-extern "C" int32_t adn_wgrad_batchable(const AdnWgradDesc* d) {
-  if (!d || d->geom == ADN_GEMM_S1) return 0;
-  return adn_wgrad_k4_batchable(d);
-}
-
-extern "C" int64_t adn_wgrad_patch_batch_workspace_bytes(const AdnWgradDesc* descs, int32_t n) {
-  for (int k = 0; descs && k < n && k < 4; ++k)
-    if (descs[k].geom == ADN_GEMM_S1) return -1;
-  return adn_wgrad_k4_patch_batch_workspace_bytes(descs, n);
-}
-
-extern "C" int adn_wgrad_patch_batch(const AdnWgradDesc* descs, int32_t n, void* stream) {
-  return adn_wgrad_k4_patch_batch(descs, n, stream);
-}
-
-extern "C" int32_t adn_wgrad_batch_sq_count(const AdnWgradDesc* d) {
-  if (!d || d->geom == ADN_GEMM_S1) return 0;
-  return adn_wgrad_k4_batch_sq_count(d);
-}
-
-extern "C" int adn_wgrad_batch(const AdnWgradDesc* descs, int32_t n, void* stream) {
-  return adn_wgrad_k4_batch(descs, n, stream);
-}
-
 extern "C" int64_t adn_wgrad_workspace_bytes(const AdnWgradDesc* d) {
   if (wvalidate(d) != ADN_OK) return -1;
-  if (d->geom != ADN_GEMM_S1) return adn_wgrad_k4_workspace_bytes(d);
-  int ns;
-  int64_t oe;
-  if (adn_wgrad_s1p_plan(d, &ns, &oe)) return ns > 1 ? (int64_t)ns * oe * 4 : 0;
-  WPlan pl;
-  make_wplan(d, &pl);
-  return pl.slab_bytes;
+  return wroute(d).slab_bytes();
 }
 
 extern "C" int adn_wgrad(const AdnWgradDesc* d, void* stream) {
   int rc = wvalidate(d);
   if (rc != ADN_OK) return rc;
-  if (d->geom != ADN_GEMM_S1) return adn_wgrad_k4(d, stream);
-  {
-    int ns;
-    int64_t oe;
-    if (adn_wgrad_s1p_plan(d, &ns, &oe)) {
-      const int64_t need = ns > 1 ? (int64_t)ns * oe * 4 : 0;
-      ADN_CHECK_ARG(need == 0 || (d->workspace && d->workspace_bytes >= need), "adn_wgrad: workspace too small (%lld < %lld)",
-                    (long long)d->workspace_bytes, (long long)need);
-      rc = adn_wgrad_s1p_launch(d, ns, oe, stream);
-      if (rc != ADN_OK) return rc;
-      if (ns > 1) {
-        int64_t blocks = adn_cdiv(adn_cdiv(oe, 4), 256);
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                           reinterpret_cast<const float*>(d->workspace), d->dw, oe, ns);
-        ADN_CHECK_LAUNCH();
-      }
-      return ADN_OK;
-    }
+  const WRoute r = wroute(d);
+  const int64_t need = r.slab_bytes();
+  ADN_CHECK_ARG(need == 0 || (d->workspace && d->workspace_bytes >= need), "adn_wgrad: workspace too small (%lld < %lld)",
+                (long long)d->workspace_bytes, (long long)need);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (r.patch) {
+    rc = adn_wgrad_patch_launch(d, r.nsplit, r.out_elems, stream);
+    if (rc != ADN_OK) return rc;
+    return slab_sum(reinterpret_cast<const float*>(d->workspace), d->dw, r.out_elems, r.nsplit, sq_of(d), st);
   }
+  if (d->dtype == ADN_BF16) return wrun<uint16_t>(d, r.pl, st);
+  return wrun<float>(d, r.pl, st);
+}
+
+// doubles adn_wgrad leaves in d->sq_partials: one per workgroup of the launch that writes the final dW (S1: none, see sq_of)
+extern "C" int32_t adn_wgrad_sq_count(const AdnWgradDesc* d) {
+  if (!d || d->geom == ADN_GEMM_S1 || wvalidate(d) != ADN_OK) return 0;
+  const WRoute r = wroute(d);
+  if (r.nsplit > 1) return (int32_t)slab_sum_blocks(r.out_elems, true);
+  const int cv = d->c_valid > 0 ? d->c_valid : d->C0 + d->C1;
+  if (!r.patch && r.pl.mfma && cv == d->C0 + d->C1) return r.pl.tiles_r * r.pl.tiles_c;
+  return 0;
+}
+
+extern "C" int64_t adn_wgrad_patch_batch_workspace_bytes(const AdnWgradDesc* descs, int32_t n) {
+  int ns[4];
+  int64_t oe[4], off[4], total;
+  if (!descs || n < 1 || n > 4 || !patch_batch_plan(descs, n, ns, oe, off, &total)) return -1;
+  return total;
+}
+
+extern "C" int adn_wgrad_patch_batch(const AdnWgradDesc* descs, int32_t n, void* stream) {
+  ADN_CHECK_ARG(descs && n >= 1 && n <= 4, "adn_wgrad_patch_batch: 1 .. 4 problems (got %d)", n);
+  int ns[4];
+  int64_t oe[4], off[4], total;
+  ADN_CHECK_ARG(patch_batch_plan(descs, n, ns, oe, off, &total),
+                "adn_wgrad_patch_batch: a problem is not a patch-staged layer (adn_wgrad_patch_batch_workspace_bytes < 0)");
+  ADN_CHECK_ARG(total == 0 || (descs[0].workspace && descs[0].workspace_bytes >= total),
+                "adn_wgrad_patch_batch: workspace too small (%lld < %lld)", (long long)descs[0].workspace_bytes, (long long)total);
+  float* out[4];
+  for (int k = 0; k < n; ++k)
+    out[k] = ns[k] > 1 ? reinterpret_cast<float*>(reinterpret_cast<char*>(descs[0].workspace) + off[k]) : descs[k].dw;
+  int rc = adn_wgrad_k4p_batch_launch(descs, n, ns, out, stream);
+  if (rc != ADN_OK) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  for (int k = 0; k < n; ++k) {
+    // known gap: a problem whose split count rounds down to 1 has no slab sum, hence leaves NO norm partials behind
+    rc = slab_sum(out[k], descs[k].dw, oe[k], ns[k], descs[k].sq_partials, st);
+    if (rc != ADN_OK) return rc;
+  }
+  return ADN_OK;
+}
+
+// 0: `d` cannot ride in adn_wgrad_batch; 1 / 2: it can, in the general / power-of-two-image ("fast") form of the
+// tap-staged MFMA kernel (a launch holds problems of ONE class).  Inside a batch every problem runs UNSPLIT -- the other
+// problems of the launch provide the parallelism a lone launch gets from splitting the pixels -- so it writes the final dW
+// (no slab sum) and tiles_r * tiles_c norm partials (adn_wgrad_batch_sq_count).  k4 pair, bf16 only.
+extern "C" int32_t adn_wgrad_batchable(const AdnWgradDesc* d) {
+  if (!d || d->geom == ADN_GEMM_S1 || wvalidate(d) != ADN_OK || d->dtype != ADN_BF16) return 0;
+  if (d->c_valid > 0 && d->c_valid != d->C0 + d->C1) return 0;
+  const WRoute r = wroute(d);
+  if (r.patch || !r.pl.mfma || r.pl.nsplit > 2) return 0;             // (a layer that wants many pixel splits is not a small one)
+  return r.pl.fast ? 2 : 1;
+}
+
+extern "C" int32_t adn_wgrad_batch_sq_count(const AdnWgradDesc* d) {
+  if (!adn_wgrad_batchable(d)) return 0;
   WPlan pl;
   make_wplan(d, &pl);
-  ADN_CHECK_ARG(pl.slab_bytes == 0 || (d->workspace && d->workspace_bytes >= pl.slab_bytes),
-                "adn_wgrad: workspace too small (%lld < %lld)", (long long)d->workspace_bytes,
-                (long long)pl.slab_bytes);
+  return pl.tiles_r * pl.tiles_c;
+}
+
+extern "C" int adn_wgrad_batch(const AdnWgradDesc* descs, int32_t n, void* stream) {
+  ADN_CHECK_ARG(descs && n >= 1 && n <= kWgradBatchMax, "adn_wgrad_batch: 1 .. %d problems (got %d)", kWgradBatchMax, n);
+  WBatch b;
+  b.n = n;
+  b.first[0] = 0;
+  const int32_t cls = adn_wgrad_batchable(descs);
+  for (int k = 0; k < n; ++k) {
+    const int32_t c = adn_wgrad_batchable(descs + k);
+    ADN_CHECK_ARG(c != 0, "adn_wgrad_batch: problem %d is not batchable (adn_wgrad_batchable)", k);
+    ADN_CHECK_ARG(c == cls, "adn_wgrad_batch: problem %d is of class %d, problem 0 of class %d (one class per launch)", k, c, cls);
+    WPlan pl;
+    make_wplan(descs + k, &pl);
+    pl.nsplit = 1;
+    fill_wparams(descs + k, pl, b.p[k]);
+    b.first[k + 1] = b.first[k] + pl.tiles_r * pl.tiles_c;
+  }
+  for (int k = n; k < kWgradBatchMax; ++k) {
+    b.p[k] = b.p[0];
+    b.first[k + 1] = b.first[n];
+  }
+  constexpr int lds = wgrad_lds<uint16_t>();
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d->dtype == ADN_BF16) return wrun<uint16_t>(d, pl, st);
-  return wrun<float>(d, pl, st);
+  if (cls == 2) {
+    ADN_SET_LDS_ONCE(lds, &wgrad_mfma_batch_kernel<uint16_t, true>);
+    hipLaunchKernelGGL((wgrad_mfma_batch_kernel<uint16_t, true>), dim3((unsigned)b.first[n]), dim3(256), lds, st, b);
+  } else {
+    ADN_SET_LDS_ONCE(lds, &wgrad_mfma_batch_kernel<uint16_t, false>);
+    hipLaunchKernelGGL((wgrad_mfma_batch_kernel<uint16_t, false>), dim3((unsigned)b.first[n]), dim3(256), lds, st, b);
+  }
+  ADN_CHECK_LAUNCH();
+  return ADN_OK;
 }

@@ -1,5 +1,8 @@
-// Patch-staged weight-gradient kernel of the 3 x 3 stride-1 convolutions (DoubleConv nets; bf16, gfx950).
+// Patch-staged weight-gradient kernels (bf16, gfx950), one per conv geometry: wgrad_s1_patch_kernel for the 3 x 3 stride-1
+// convolutions of the DoubleConv nets (first half of this file) and wgrad_k4_patch_kernel for the k4/s2/p1 pair of the
+// U-Net (second half), with their plans and launches.  wgrad.hip decides which layers come here.
 //
+// ---- 3 x 3 stride 1 ----
 //   dW[r][tap][c] = sum over pixels p of  dz[p][r] * in[p + tap][c]
 //
 // Why: the tap-staged kernel (wgrad.hip) lays the 9 taps out as column tiles, so every workgroup stages its own 64-pixel
@@ -22,6 +25,7 @@
 #include <type_traits>
 
 #include "adn_common.h"
+#include "wgrad_internal.h"
 
 namespace {
 
@@ -201,7 +205,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_s1_patch_kernel(SParams p) {
 // transposed conv: plain = layer input, gathered = dZ) -----------------------------------------------------------------
 //   dW[r][tap][c] = sum over small-grid pixels (i, j) of  plain[i, j][r] * gath[2i - 1 + ky, 2j - 1 + kx][c]
 // Same idea on 8 x 8 small-grid tiles: a workgroup owns 64(r) x 32(c) x 16 taps and stages, per tile, plain[64 px][64 r]
-// (8 KiB) and the 18 x 18 gathered patch of 32 channels (20.25 KiB) once -- the tap-staged kernel (wgrad_k4.hip) moves
+// (8 KiB) and the 18 x 18 gathered patch of 32 channels (20.25 KiB) once -- the tap-staged kernel (wgrad.hip) moves
 // 16 KiB + 16 KiB per 64 pixels for every one of its 128-column (tap, c) tiles.  The patch is stored as four planes by
 // (row parity, column parity) of 9 x 9 pixels, 64-byte pixels: tap (ky, kx) of output pixel (y, x) is plane
 // (ky & 1, kx & 1), pixel (y + (ky >> 1), x + (kx >> 1)), so the 4 consecutive output columns a lane group transposes
@@ -482,10 +486,8 @@ bool patch_enabled() {
   return on != 0;
 }
 
-}  // namespace
-
 // Eligibility + plan: bf16, 3 x 3, one plain source, every channel count a multiple of 64, images tileable by 8 x 16.
-bool adn_wgrad_s1p_plan(const AdnWgradDesc* d, int* nsplit, int64_t* out_elems) {
+bool s1p_plan(const AdnWgradDesc* d, int* nsplit, int64_t* out_elems) {
   if (!patch_enabled()) return false;
   if (d->dtype != ADN_BF16 || d->geom != ADN_GEMM_S1 || d->ks != 3) return false;
   if (d->R1 != 0 || d->R0 % 64 != 0 || d->C0 % 64 != 0 || d->C1 % 64 != 0) return false;
@@ -504,7 +506,7 @@ bool adn_wgrad_s1p_plan(const AdnWgradDesc* d, int* nsplit, int64_t* out_elems) 
   return true;
 }
 
-int adn_wgrad_s1p_launch(const AdnWgradDesc* d, int nsplit, int64_t out_elems, void* stream) {
+int s1p_launch(const AdnWgradDesc* d, int nsplit, int64_t out_elems, void* stream) {
   SParams p;
   p.dz = d->plain0;
   p.in0 = d->gath0;
@@ -531,7 +533,7 @@ int adn_wgrad_s1p_launch(const AdnWgradDesc* d, int nsplit, int64_t out_elems, v
 }
 
 // k4 s2 p1 pair: bf16, every channel count a multiple of 64 (gathered: 32), small grid tileable by 8 x 8.
-bool adn_wgrad_k4p_plan(const AdnWgradDesc* d, int* nsplit, int64_t* out_elems) {
+bool k4p_plan(const AdnWgradDesc* d, int* nsplit, int64_t* out_elems) {
   if (!patch_enabled()) return false;
   if (d->dtype != ADN_BF16 || d->geom != 0) return false;
   if (d->R0 % 64 != 0 || d->R1 % 64 != 0 || d->C0 % 32 != 0 || d->C1 % 32 != 0) return false;
@@ -552,7 +554,7 @@ bool adn_wgrad_k4p_plan(const AdnWgradDesc* d, int* nsplit, int64_t* out_elems) 
   return true;
 }
 
-static void fill_k4p(const AdnWgradDesc* d, int nsplit, int64_t out_elems, float* outp, KParams4& p) {
+void fill_k4p(const AdnWgradDesc* d, int nsplit, int64_t out_elems, float* outp, KParams4& p) {
   p.plain0 = d->plain0;
   p.plain1 = d->plain1;
   p.gath0 = d->gath0;
@@ -574,6 +576,31 @@ static void fill_k4p(const AdnWgradDesc* d, int nsplit, int64_t out_elems, float
   p.out_elems = out_elems;
 }
 
+int k4p_launch(const AdnWgradDesc* d, int nsplit, int64_t out_elems, void* stream) {
+  KParams4 p;
+  fill_k4p(d, nsplit, out_elems, nsplit > 1 ? reinterpret_cast<float*>(d->workspace) : d->dw, p);
+  constexpr int lds = 2 * (64 * 128 + 24 * 1024);
+  if (g_spread) {
+    ADN_SET_LDS_ONCE(lds, &wgrad_k4_patch_kernel<true>);
+    hipLaunchKernelGGL(wgrad_k4_patch_kernel<true>, dim3(p.nrb * p.ncb * nsplit), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), p);
+  } else {
+    ADN_SET_LDS_ONCE(lds, &wgrad_k4_patch_kernel<false>);
+    hipLaunchKernelGGL(wgrad_k4_patch_kernel<false>, dim3(p.nrb * p.ncb * nsplit), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), p);
+  }
+  ADN_CHECK_LAUNCH();
+  return ADN_OK;
+}
+
+}  // namespace
+
+bool adn_wgrad_patch_plan(const AdnWgradDesc* d, int* nsplit, int64_t* out_elems) {
+  return d->geom == ADN_GEMM_S1 ? s1p_plan(d, nsplit, out_elems) : k4p_plan(d, nsplit, out_elems);
+}
+
+int adn_wgrad_patch_launch(const AdnWgradDesc* d, int nsplit, int64_t out_elems, void* stream) {
+  return d->geom == ADN_GEMM_S1 ? s1p_launch(d, nsplit, out_elems, stream) : k4p_launch(d, nsplit, out_elems, stream);
+}
+
 // n <= 4 problems in one launch; nsplit[k] pixel splits and the slab (or, unsplit, dW) base out[k] per problem
 int adn_wgrad_k4p_batch_launch(const AdnWgradDesc* descs, int n, const int* nsplit, float* const* out, void* stream) {
   ADN_CHECK_ARG(n >= 1 && n <= kK4BatchMax, "adn_wgrad_patch_batch: 1 .. %d problems", kK4BatchMax);
@@ -592,39 +619,6 @@ int adn_wgrad_k4p_batch_launch(const AdnWgradDesc* descs, int n, const int* nspl
   constexpr int lds = 2 * (64 * 128 + 24 * 1024);
   ADN_SET_LDS_ONCE(lds, &wgrad_k4_patch_batch_kernel);
   hipLaunchKernelGGL(wgrad_k4_patch_batch_kernel, dim3((unsigned)b.first[n]), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), b);
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
-}
-
-int adn_wgrad_k4p_launch(const AdnWgradDesc* d, int nsplit, int64_t out_elems, void* stream) {
-  KParams4 p;
-  p.plain0 = d->plain0;
-  p.plain1 = d->plain1;
-  p.gath0 = d->gath0;
-  p.gath1 = d->gath1;
-  p.R0 = d->R0;
-  p.R1 = d->R1;
-  p.C0 = d->C0;
-  p.C1 = d->C1;
-  p.B = d->B;
-  p.Hs = d->Hs;
-  p.Ws = d->Ws;
-  p.nsplit = nsplit;
-  p.nrb = (d->R0 + d->R1) / 64;
-  p.ncb = (d->C0 + d->C1) / 32;
-  p.tpr = d->Ws / 8;
-  p.tpi = (d->Hs / 8) * p.tpr;
-  p.tiles_total = d->B * p.tpi;
-  p.out = nsplit > 1 ? reinterpret_cast<float*>(d->workspace) : d->dw;
-  p.out_elems = out_elems;
-  constexpr int lds = 2 * (64 * 128 + 24 * 1024);
-  if (g_spread) {
-    ADN_SET_LDS_ONCE(lds, &wgrad_k4_patch_kernel<true>);
-    hipLaunchKernelGGL(wgrad_k4_patch_kernel<true>, dim3(p.nrb * p.ncb * nsplit), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), p);
-  } else {
-    ADN_SET_LDS_ONCE(lds, &wgrad_k4_patch_kernel<false>);
-    hipLaunchKernelGGL(wgrad_k4_patch_kernel<false>, dim3(p.nrb * p.ncb * nsplit), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), p);
-  }
   ADN_CHECK_LAUNCH();
   return ADN_OK;
 }

@@ -146,3 +146,48 @@ def test_optim_state_groups_and_legacy_flat_layout():
     assert v[8:13].tolist() == [8, 10, 12, 14, 16]
     with pytest.raises(ValueError, match='matches neither'):
         optim_state.import_legacy_flat({'exp_avg': torch.zeros(17), 'exp_avg_sq': torch.zeros(17), 'step': 1}, meta, m, v)
+
+
+def _wgrad_plan_tool():
+    import importlib.util
+    path = os.path.join(os.path.dirname(GOLDEN), '..', 'tools', 'wgrad_plan_table.py')
+    spec = importlib.util.spec_from_file_location('wgrad_plan_table', os.path.abspath(path))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_wgrad_plans_match_recorded_table():
+    """The weight-gradient plan queries (host only) answer what tests/golden/wgrad_plans.json recorded from the library
+    before the tap-staged kernels of the two geometries were merged into one source (tools/wgrad_plan_table.py writes the
+    table from any build).  Workspace bytes pin the split count, hence the summation order, hence the bits of dW."""
+    tool = _wgrad_plan_tool()
+    table = json.load(open(os.path.join(GOLDEN, 'wgrad_plans.json')))
+    assert len(table['rows']) >= 80 and len(table['groups']) >= 2
+    for r in table['rows']:
+        got = tool.query_row(r)
+        assert got == {k: r[k] for k in got}, r['name']
+    for g, v in table['groups'].items():
+        assert tool.query_group(v['rows']) == v['workspace_bytes'], g
+    # the recorded table must itself hold what it is meant to pin
+    by_name = {r['name']: r for r in table['rows']}
+    assert table['groups']['patch_L3_L2_L1']['workspace_bytes'] > 0 and table['groups']['patch_D1_D2_D3']['workspace_bytes'] > 0
+    assert table['groups']['not_patch_s1']['workspace_bytes'] == -1
+    assert by_name['unet256_L1_bf16']['sq_count'] > 0 and by_name['unet256_L5_bf16']['batchable'] > 0
+    for r in table['rows']:
+        if r['ks']:
+            assert (r['sq_count'], r['batchable'], r['batch_sq_count']) == (0, 0, 0), r['name']
+
+
+def test_wgrad_plans_with_patch_kernels_off_match_recorded_table():
+    """ADN_WGRAD_PATCH=0 (read once per process, hence the child): every layer takes the tap-staged plan."""
+    import subprocess
+    import sys
+    table = json.load(open(os.path.join(GOLDEN, 'wgrad_plans.json')))
+    tool = os.path.abspath(os.path.join(os.path.dirname(GOLDEN), '..', 'tools', 'wgrad_plan_table.py'))
+    out = subprocess.run([sys.executable, tool, '--query', 'rows_patch_off'], env=dict(os.environ, ADN_WGRAD_PATCH='0'),
+                         capture_output=True, text=True, check=True).stdout
+    assert len(table['rows_patch_off']) >= 10
+    assert json.loads(out) == table['rows_patch_off']
+    on = {r['name']: r for r in table['rows']}
+    assert any(r['workspace_bytes'] != on[r['name']]['workspace_bytes'] for r in table['rows_patch_off'])

@@ -1,6 +1,6 @@
 """Static census of EXPOSED LDS round trips in the K loops of the MFMA kernels (no GPU needed).
 
-    python tools/isa_lds_waits.py [igemm wgrad_s1p wgrad_k4 wgrad attn_mfma mx8]
+    python tools/isa_lds_waits.py [igemm wgrad_patch wgrad attn_mfma mx8]
 
 Compiles each csrc/<name>.hip to gfx950 assembly (`hipcc -S --cuda-device-only`) and, per kernel, looks at the code between
 its first and last `s_barrier` (the K loop, for the unrolled kernels plus a little of the epilogue): counts the MFMAs, the
@@ -61,7 +61,7 @@ def census(lines):
 
 
 def main():
-    names = sys.argv[1:] or ['igemm', 'wgrad_s1p', 'wgrad_k4', 'wgrad', 'attn_mfma', 'mx8']
+    names = sys.argv[1:] or ['igemm', 'wgrad_patch', 'wgrad', 'attn_mfma', 'mx8']
     filt = shutil.which('c++filt') or shutil.which('llvm-cxxfilt')
     tmp = tempfile.mkdtemp()
     for n in names:
