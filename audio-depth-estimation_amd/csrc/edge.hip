@@ -1,6 +1,6 @@
 // Thin outermost layers of the U-Net generator on the bf16 path (gfx950): the first Conv2d(k4,s2,p1) with 2 input
-// channels and the last ConvTranspose2d(k4,s2,p1) with 1 output channel (/root/reference/models/unetbaseline_model.py
-// :187-198).  With K = 32 (16 taps x 2 channels) resp. N = 1 these layers do 0.5 % of the step's FLOPs but stream the
+// channels and the last ConvTranspose2d(k4,s2,p1) with 1 output channel (models/unetbaseline_model.py:187-198 of the
+// reference).  With K = 32 (16 taps x 2 channels) resp. N = 1 these layers do 0.5 % of the step's FLOPs but stream the
 // two widest activations of the network (B x 128 x 128 x 64 each way), so every kernel here is HBM-bound: one MFMA per
 // 16 pixels, everything else is about moving whole 64-byte / 128-byte pieces of NHWC rows once.
 //
@@ -16,8 +16,10 @@
 //
 // Transposed-output trick (l0_fwd, d0_dgrad): the MFMA computes out^T = W * window^T, so a lane ends up with one
 // PIXEL and 4 consecutive accumulator rows = 4 channels per tile; the weight rows are permuted such that the four tiles
-// of a 64-channel segment give lane (pixel n, group q) channels q*8..q*8+7 and 32+q*8..32+q*8+7: two 16-byte pieces,
-// the four lanes of a pixel together write 64 contiguous bytes per store instruction.
+// of a 64-channel segment give lane (pixel n, group q) channels q*8..q*8+7 and 32+q*8..32+q*8+7: two 16-byte pieces.
+// d0_dgrad stores them as they are (the four lanes of a pixel write 64 contiguous bytes per store instruction); l0_fwd,
+// which has nothing else to do, turns its 16-pixel x 128-byte tile through LDS so that a store instruction writes 1 KiB
+// of consecutive memory, lane l the l-th 16-byte piece.
 #include "epilogue.h"
 
 namespace {
@@ -62,9 +64,23 @@ __device__ __forceinline__ void load_bf16x8(const uint16_t* p, float* f) {
 __global__ __launch_bounds__(256) void l0_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w, int B,
                                                      int Hs, int Ws, float slope, uint16_t* out_leaky,
                                                      uint16_t* out_relu) {
+  // Output tile of a 16-pixel group = 2 KiB of consecutive NHWC memory, staged per wave: lane (n, q) writes its pieces
+  // h*4 + q of pixel n, lane l reads back pieces l and 64 + l of the tile (piece = pixel * 8 + 16-byte piece).  The piece
+  // index inside a pixel is XORed with (pixel >> 1) & 7: both directions are free of bank conflicts.  LDS operations of
+  // one wave complete in order, so the staging needs no barrier, only that the compiler keeps the program order.
+  __shared__ __attribute__((aligned(16))) char stage_all[4][2048];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = lane & 15, q = lane >> 4;
   const int Hl = 2 * Hs, Wl = 2 * Ws;
+  char* stage = stage_all[wave];
+  u32x4_t* st_w[2];
+  const u32x4_t* st_r[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    st_w[h] = reinterpret_cast<u32x4_t*>(stage + n * 128 + (((h * 4 + q) ^ ((n >> 1) & 7)) << 4));
+    const int pc = h * 64 + lane, px = pc >> 3;
+    st_r[h] = reinterpret_cast<const u32x4_t*>(stage + px * 128 + (((pc & 7) ^ ((px >> 1) & 7)) << 4));
+  }
   bf16x8_t wf[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
@@ -102,26 +118,42 @@ __global__ __launch_bounds__(256) void l0_fwd_kernel(const float* __restrict__ x
 #pragma unroll
     for (int t = 0; t < 4; ++t)
       acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[t], bfr, f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-    const int64_t pix = ((int64_t)b * Hs + oy) * Ws + ox;
+    const int64_t tile = (((int64_t)b * Hs + oy) * Ws + jg * 16) * 64 + lane * 8;      // this lane's first piece
+    float v[2][8];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      float v[8], o[8];
+    for (int h = 0; h < 2; ++h)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        v[e] = acc[2 * h][e];
-        v[4 + e] = acc[2 * h + 1][e];
+        v[h][e] = acc[2 * h][e];
+        v[h][4 + e] = acc[2 * h + 1][e];
       }
-      const int64_t idx = pix * 64 + h * 32 + q * 8;
-      if (out_leaky) {
+    if (out_leaky) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = v[e] > 0.f ? v[e] : v[e] * slope;
-        store_bf16x8(out_leaky + idx, o);
-      }
-      if (out_relu) {
+      for (int h = 0; h < 2; ++h) {
+        float o[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = fmaxf(v[e], 0.f);
-        store_bf16x8(out_relu + idx, o);
+        for (int e = 0; e < 8; ++e) o[e] = v[h][e] > 0.f ? v[h][e] : v[h][e] * slope;
+        *st_w[h] = Chunk<uint16_t>::pack(o);
       }
+      asm volatile("" ::: "memory");
+      const u32x4_t p0 = *st_r[0], p1 = *st_r[1];
+      asm volatile("" ::: "memory");
+      *reinterpret_cast<u32x4_t*>(out_leaky + tile) = p0;
+      *reinterpret_cast<u32x4_t*>(out_leaky + tile + 512) = p1;
+    }
+    if (out_relu) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        float o[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = fmaxf(v[h][e], 0.f);
+        *st_w[h] = Chunk<uint16_t>::pack(o);
+      }
+      asm volatile("" ::: "memory");
+      const u32x4_t p0 = *st_r[0], p1 = *st_r[1];
+      asm volatile("" ::: "memory");
+      *reinterpret_cast<u32x4_t*>(out_relu + tile) = p0;
+      *reinterpret_cast<u32x4_t*>(out_relu + tile + 512) = p1;
     }
    }
   }
@@ -292,7 +324,9 @@ struct TWParams {
   float* slab;       // [blocks][16*CT][C0+C1]
 };
 
-template <int CT, int NT0, int NT1>
+// RELU0: plain0 holds the values before the ReLU; its fragments are clamped on their raw bits after the transposed
+// read (signed 16-bit max with 0: an element whose sign bit is set becomes +0, what fmaxf(v, 0.f) stores).
+template <int CT, int NT0, int NT1, bool RELU0>
 __global__ __launch_bounds__(256) void thin_wgrad_kernel(TWParams p) {
   constexpr int NT = NT0 + NT1;
   constexpr int RB0 = NT0 * 32, RB1 = NT1 * 32;          // tile row bytes of the two plain sources
@@ -392,6 +426,9 @@ __global__ __launch_bounds__(256) void thin_wgrad_kernel(TWParams p) {
       const s16x4_t hi =
           __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(a0 + 4 * rb));
       s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      if constexpr (RELU0) {
+        if (t < NT0) v = __builtin_elementwise_max(v, s16x8_t{0, 0, 0, 0, 0, 0, 0, 0});
+      }
       const bf16x8_t bfr = *reinterpret_cast<bf16x8_t*>(&v);
 #pragma unroll
       for (int m = 0; m < CT; ++m) acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[m], bfr, acc[m][t], 0, 0, 0);
@@ -507,10 +544,11 @@ extern "C" int64_t adn_thin_wgrad_workspace_bytes(int32_t B, int32_t Hs, int32_t
   return (int64_t)edge_blocks((int64_t)B * Hs * (Ws / 32), kWgradBlocks) * 16 * ct * (c0 + c1) * 4;
 }
 
-extern "C" int adn_thin_wgrad(const float* thin, int32_t ct, const void* plain0, int32_t c0, const void* plain1,
-                              int32_t c1, int32_t B, int32_t Hs, int32_t Ws, float* dw, void* workspace,
-                              int64_t workspace_bytes, void* stream) {
+extern "C" int adn_thin_wgrad_ex(const float* thin, int32_t ct, const void* plain0, int32_t c0, const void* plain1,
+                                 int32_t c1, int32_t B, int32_t Hs, int32_t Ws, float* dw, void* workspace,
+                                 int64_t workspace_bytes, int32_t relu_plain0, void* stream) {
   ADN_CHECK_ARG(thin && plain0 && dw && workspace && (c1 == 0 || plain1), "adn_thin_wgrad: null operand");
+  ADN_CHECK_ARG(!relu_plain0 || ct == 1, "adn_thin_wgrad: relu_plain0 is for the ct 1 form (plain0 = an activation)");
   ADN_CHECK_ARG(B > 0 && Hs > 0 && Ws > 0 && Ws % 32 == 0, "adn_thin_wgrad: bad shape B=%d Hs=%d Ws=%d (Ws %% 32)", B, Hs,
                 Ws);
   ADN_CHECK_ARG((ct == 1 && c0 == 64 && c1 == 64) || (ct == 2 && c0 == 64 && c1 == 0),
@@ -533,16 +571,25 @@ extern "C" int adn_thin_wgrad(const float* thin, int32_t ct, const void* plain0,
   // LDS: 4 waves x 2 staging buffers x 32 pixels x (c0 + c1) bf16, reused as the [4][rows][ctot] f32 reduction tile
   const int stage = 4 * 2 * 32 * ctot * 2, redb = 4 * rows * ctot * 4;
   const int lds = stage > redb ? stage : redb;
-  if (ct == 1) {
-    ADN_SET_LDS_ONCE(lds, &thin_wgrad_kernel<1, 4, 4>);
-    hipLaunchKernelGGL((thin_wgrad_kernel<1, 4, 4>), dim3(nblk), dim3(256), lds, st, p);
+  if (ct == 1 && relu_plain0) {
+    ADN_SET_LDS_ONCE(lds, &thin_wgrad_kernel<1, 4, 4, true>);
+    hipLaunchKernelGGL((thin_wgrad_kernel<1, 4, 4, true>), dim3(nblk), dim3(256), lds, st, p);
+  } else if (ct == 1) {
+    ADN_SET_LDS_ONCE(lds, &thin_wgrad_kernel<1, 4, 4, false>);
+    hipLaunchKernelGGL((thin_wgrad_kernel<1, 4, 4, false>), dim3(nblk), dim3(256), lds, st, p);
   } else {
-    ADN_SET_LDS_ONCE(lds, &thin_wgrad_kernel<2, 4, 0>);
-    hipLaunchKernelGGL((thin_wgrad_kernel<2, 4, 0>), dim3(nblk), dim3(256), lds, st, p);
+    ADN_SET_LDS_ONCE(lds, &thin_wgrad_kernel<2, 4, 0, false>);
+    hipLaunchKernelGGL((thin_wgrad_kernel<2, 4, 0, false>), dim3(nblk), dim3(256), lds, st, p);
   }
   ADN_CHECK_LAUNCH();
   hipLaunchKernelGGL(thin_wgrad_sum_kernel, dim3((unsigned)adn_cdiv(rows * ctot, 16)), dim3(256), 0, st, p.slab, nblk,
                      rows, ctot, dw);
   ADN_CHECK_LAUNCH();
   return ADN_OK;
+}
+
+extern "C" int adn_thin_wgrad(const float* thin, int32_t ct, const void* plain0, int32_t c0, const void* plain1,
+                              int32_t c1, int32_t B, int32_t Hs, int32_t Ws, float* dw, void* workspace,
+                              int64_t workspace_bytes, void* stream) {
+  return adn_thin_wgrad_ex(thin, ct, plain0, c0, plain1, c1, B, Hs, Ws, dw, workspace, workspace_bytes, 0, stream);
 }

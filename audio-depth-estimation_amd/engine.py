@@ -112,6 +112,11 @@ class UNetEngine(FlatParamEngine):
                           and (W // 2) % 32 == 0 and not os.environ.get('ADN_NO_EDGE'))
         if self.edge_path:
             self.cin_pad, self.cout_pad = Cin, cout0
+        # One copy of the outermost activation: every reader of level 0's skip operand is then an edge kernel that takes
+        # the LeakyReLU copy ad[0] and applies the ReLU itself (relu(leaky(v)) == relu(v) bit for bit for a positive
+        # slope), so rd[0] is neither allocated nor written.  ADN_L0_TWO_COPIES=1 keeps the separate ReLU copy (A/B).
+        self.skip0_leaky = (self.edge_path and self.n1_path and not self._no_skip(0)
+                            and not os.environ.get('ADN_L0_TWO_COPIES'))
         self.x_nhwc = None if self.edge_path else torch.empty(B, H, W, self.cin_pad, dtype=T, device=dev)
         batching_patch = (T == torch.bfloat16 and not os.environ.get('ADN_NO_WGRAD_BATCH')
                           and not os.environ.get('ADN_NO_PATCH_BATCH'))
@@ -127,7 +132,9 @@ class UNetEngine(FlatParamEngine):
             lv.update(down_ypad=cd_in_p, up_ypad=cu_out_p)
             act = lambda c, h=hs, w_=wsz: torch.empty(B, h, w_, c, dtype=T, device=dev)
             lv['ad'] = act(cd_out) if i < n - 1 else None
-            lv['rd'] = None if self._no_skip(i) else act(cd_out)
+            lv['rd'] = None if self._no_skip(i) or (i == 0 and self.skip0_leaky) else act(cd_out)
+            # the skip operand as its readers get it (level 0 with skip0_leaky: before the ReLU, see _skip_relu)
+            lv['skip'] = lv['ad'] if i == 0 and self.skip0_leaky else lv['rd']
             lv['Gd'] = act(cd_out)
             lv['zd'] = act(cd_out) if lv['bn_d'] is not None else None
             big = lambda c, h=hs, w_=wsz: torch.empty(B, 2 * h, 2 * w_, c, dtype=T, device=dev)
@@ -249,11 +256,16 @@ class UNetEngine(FlatParamEngine):
         return self.vae is not None and i == self.n - 2
 
     def _up_inputs(self, i):
-        """Operands of level i's transposed conv: the skip rd[i] and the level below's ru[i+1] (a virtual concat)."""
+        """Operands of level i's transposed conv: the skip operand of level i and the level below's ru[i+1] (a virtual
+        concat).  The forward and the weight gradient of the layer both take them from here, with _skip_relu(i)."""
         L = self.levels
         if self._no_skip(i):
             return L[i + 1]['ru'], None
-        return L[i]['rd'], (L[i + 1]['ru'] if i < self.n - 1 else None)
+        return L[i]['skip'], (L[i + 1]['ru'] if i < self.n - 1 else None)
+
+    def _skip_relu(self, i):
+        """True when the first operand of _up_inputs(i) still needs its ReLU (the reader clamps it on load)."""
+        return i == 0 and self.skip0_leaky
 
     # ------------------------------------------------------------------ fused gradient norm
     supports_fused_norm = True
@@ -346,7 +358,7 @@ class UNetEngine(FlatParamEngine):
                 fa = self.final_act
                 if self.n1_path:
                     K.convt_n1_forward(T, B, hs, wsz, in0, in1, self._flat_slice(self.flat_p, lv['up'].weight), bias,
-                                       fa, lv['out'], ws)
+                                       fa, lv['out'], ws, relu_in0=self._skip_relu(i))
                 else:
                     K.igemm(T, GEMM_T2, B, hs, wsz, in0, in1, lv['up_t2'], C, EPI_FINAL,
                             [K.Seg(C, out0=lv['out'], bias=bias, final_act=fa)], ws)
@@ -451,14 +463,16 @@ class UNetEngine(FlatParamEngine):
                 self._bn_backward(lv, 'u', lv['bn_u'], B * 4 * hs * wsz, L[i - 1]['P_gu'], lv['Gu'], lv['zu'])
                 dz = lv['Gu']
             in0, in1 = self._up_inputs(i)
-            segs = [] if lv['rd'] is None else [K.Seg(lv['cd_out'], out0=lv['Gd'], ref=lv['rd'], slope=0.0)]
+            # (ref is only compared with 0: the LeakyReLU copy of level 0 gives the same mask as the ReLU copy)
+            segs = [] if self._no_skip(i) else [K.Seg(lv['cd_out'], out0=lv['Gd'], ref=lv['skip'], slope=0.0)]
             if i < n - 1:
                 nx = L[i + 1]
                 segs.append(K.Seg(nx['cu_out'], out0=nx['Gu'], ref=nx['ru'], slope=0.0, z=nx['zu'],
                                   mean=nx['mean_u'], istd=nx['istd_u'], partials=nx['bpart_u'],
                                   scale=nx['scale_u'], shift=nx['shift_u']))
             if i == 0 and self.edge_path:
-                K.thin_wgrad(dz, in0, in1, B, hs, wsz, self._flat_slice(self.flat_g, lv['up'].weight), ws)
+                K.thin_wgrad(dz, in0, in1, B, hs, wsz, self._flat_slice(self.flat_g, lv['up'].weight), ws,
+                             relu_plain0=self._skip_relu(i))
                 self._ready(lv['up'].weight)
                 K.d0_dgrad(dz, self._flat_slice(self.flat_p, lv['up'].weight), B, hs, wsz, segs[0], segs[1])
                 continue
@@ -519,7 +533,7 @@ class UNetEngine(FlatParamEngine):
                 self._ready(lv['down'].weight)
             if i > 0:
                 pv = L[i - 1]
-                acc = pv['rd'] is not None                # no skip above the cVAE bottleneck: the only writer of Gd
+                acc = not self._no_skip(i - 1)            # no skip above the cVAE bottleneck: the only writer of Gd
                 seg = K.Seg(pv['cd_out'], out0=pv['Gd'], ref=pv['ad'], slope=LEAKY, accumulate=acc)
                 if pv['bn_d'] is not None:
                     seg = K.Seg(pv['cd_out'], out0=pv['Gd'], ref=pv['ad'], slope=LEAKY, accumulate=acc,

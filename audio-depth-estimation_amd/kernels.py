@@ -6,6 +6,7 @@ allocated by the caller (PyTorch's caching allocator).  No CPU fallbacks.
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import torch
 
@@ -459,12 +460,18 @@ def convt_n1_workspace_bytes(B, Hs, Ws):
     return _lib.load().adn_convt_n1_workspace_bytes(B, Hs, Ws)
 
 
-def convt_n1_forward(dtype, B, Hs, Ws, in0, in1, w_master, bias, final_act, out, workspace):
+N1_RELU_IN0, N1_TWO_LAUNCH = 1, 2          # adn.h: flags of adn_convt_n1_forward_ex
+
+
+def convt_n1_forward(dtype, B, Hs, Ws, in0, in1, w_master, bias, final_act, out, workspace, relu_in0=False):
+    """Last transposed conv (Cout = 1).  ``relu_in0``: in0 holds the values before the ReLU (a LeakyReLU copy), the
+    kernel clamps it on load.  ADN_CONVT_N1_FUSED=0 takes the two-launch form (tap products through the workspace)."""
     _dev(in0, in1, w_master, bias, out, workspace)
     ev = _prof_begin()
-    _lib.call('adn_convt_n1_forward', dtype_code(dtype), B, Hs, Ws, ptr(in0), in0.shape[-1], ptr(in1),
+    flags = (N1_RELU_IN0 if relu_in0 else 0) | (N1_TWO_LAUNCH if os.environ.get('ADN_CONVT_N1_FUSED') == '0' else 0)
+    _lib.call('adn_convt_n1_forward_ex', dtype_code(dtype), B, Hs, Ws, ptr(in0), in0.shape[-1], ptr(in1),
               in1.shape[-1] if in1 is not None else 0, ptr(w_master), ptr(bias), final_act, ptr(out), ptr(workspace),
-              workspace.numel() * workspace.element_size(), _stream())
+              workspace.numel() * workspace.element_size(), flags, _stream())
     if ev is not None:
         cin = in0.shape[-1] + (in1.shape[-1] if in1 is not None else 0)
         _prof_end(ev, 'convt_n1', 2.0 * B * Hs * Ws * 16 * cin)
@@ -496,14 +503,15 @@ def thin_wgrad_workspace_bytes(B, Hs, Ws, ct, c0, c1):
     return _lib.load().adn_thin_wgrad_workspace_bytes(B, Hs, Ws, ct, c0, c1)
 
 
-def thin_wgrad(thin, plain0, plain1, B, Hs, Ws, dw, workspace):
-    """dw[c][tap*ct + t] = sum plain[.., c] * thin window; thin f32 [B,ct,2Hs,2Ws] planar, plain bf16 NHWC."""
+def thin_wgrad(thin, plain0, plain1, B, Hs, Ws, dw, workspace, relu_plain0=False):
+    """dw[c][tap*ct + t] = sum plain[.., c] * thin window; thin f32 [B,ct,2Hs,2Ws] planar, plain bf16 NHWC.
+    ``relu_plain0`` (ct = 1): plain0 holds the values before the ReLU, the kernel clamps it after the load."""
     _dev(thin, plain0, plain1, dw, workspace)
     ct = thin.shape[1]
     c0 = plain0.shape[-1]
     c1 = plain1.shape[-1] if plain1 is not None else 0
-    _lib.call('adn_thin_wgrad', ptr(thin), ct, ptr(plain0), c0, ptr(plain1), c1, B, Hs, Ws, ptr(dw), ptr(workspace),
-              workspace.numel() * workspace.element_size(), _stream())
+    _lib.call('adn_thin_wgrad_ex', ptr(thin), ct, ptr(plain0), c0, ptr(plain1), c1, B, Hs, Ws, ptr(dw), ptr(workspace),
+              workspace.numel() * workspace.element_size(), 1 if relu_plain0 else 0, _stream())
     _lib.annotate(label='edge', flops=2.0 * B * Hs * Ws * (c0 + c1) * 16 * ct)
 
 

@@ -481,12 +481,24 @@ int adn_final_act_bwd(const float* gout, const float* out, int64_t n, int32_t fi
 /* Outermost ConvTranspose2d(k4,s2,p1) with ONE output channel + bias + ReLU/Sigmoid
  * (unetbaseline_model.py:196-206), as a pointwise GEMM P[m][16 taps] = in[m][:] . W[:][tap] on the
  * small grid followed by a 4-tap gather per output pixel (col2im).  w = f32 master [C0+C1][16].
- * out: f32 [B][2Hs][2Ws].  Workspace holds P (f32 [B*Hs*Ws][16]). */
+ * out: f32 [B][2Hs][2Ws].  One launch: a workgroup keeps P of a tile of input rows (+ one halo row per side) in LDS
+ * and writes the tile's output rows.  The workspace (f32 [B*Hs*Ws][16]) holds P of the two-launch form (pointwise GEMM,
+ * then gather), which is taken on request (ADN_N1_TWO_LAUNCH) and for rows too wide for a tile in LDS; both forms give
+ * the same bits.  adn_convt_n1_forward = adn_convt_n1_forward_ex with flags 0. */
+enum {
+  ADN_N1_RELU_IN0 = 1,   /* in0 holds the values BEFORE the ReLU (e.g. a LeakyReLU copy with a positive slope): the kernel
+                            clamps it on load (elements with the sign bit set -> +0)                                     */
+  ADN_N1_TWO_LAUNCH = 2  /* the two-launch form through the workspace (A/B reference of the one-launch form)             */
+};
 int64_t adn_convt_n1_workspace_bytes(int32_t B, int32_t Hs, int32_t Ws);
 int adn_convt_n1_forward(int32_t dtype, int32_t B, int32_t Hs, int32_t Ws, const void* in0, int32_t C0,
                          const void* in1, int32_t C1, const float* w, const float* bias,
                          int32_t final_act, float* out, void* workspace, int64_t workspace_bytes,
                          void* stream);
+int adn_convt_n1_forward_ex(int32_t dtype, int32_t B, int32_t Hs, int32_t Ws, const void* in0, int32_t C0,
+                            const void* in1, int32_t C1, const float* w, const float* bias,
+                            int32_t final_act, float* out, void* workspace, int64_t workspace_bytes,
+                            int32_t flags, void* stream);
 /* Thin outermost layers of unet_256 on the bf16 path (csrc/edge.hip): HBM-bound kernels, one MFMA per 16 pixels, the
  * thin operand read as planar f32 and rounded to bf16 in registers (replace the channel-padded adn_igemm / adn_wgrad
  * calls of the first Conv2d(2->64,k4,s2,p1) and the last ConvTranspose2d(128->1,k4,s2,p1),
@@ -505,11 +517,16 @@ int adn_d0_dgrad(const float* dz, const float* w, int32_t B, int32_t Hs, int32_t
 /* adn_thin_wgrad: dw[c][tap*ct_n + ct] = sum over pixels plain[b,i,j,c] * thin[b,ct,2i-1+kh,2j-1+kw]; thin f32
  *   [B][ct_n][2Hs][2Ws], plain0 / plain1 bf16 [B][Hs][Ws][c0 | c1].  (ct_n, c0, c1) = (1, 64, 64): weight gradient of the
  *   last transposed conv (thin = dz); (2, 64, 0): of the first conv (plain = its output gradient, thin = the network
- *   input).  Deterministic (per-workgroup slabs in the workspace + fixed-order sum).  Ws % 32 == 0. */
+ *   input).  Deterministic (per-workgroup slabs in the workspace + fixed-order sum).  Ws % 32 == 0.
+ *   adn_thin_wgrad_ex, relu_plain0 != 0 (ct_n = 1 only): plain0 holds the values before the ReLU and is clamped after
+ *   the load, as ADN_N1_RELU_IN0 does for the forward of the same layer.  adn_thin_wgrad = relu_plain0 0. */
 int64_t adn_thin_wgrad_workspace_bytes(int32_t B, int32_t Hs, int32_t Ws, int32_t ct_n, int32_t c0, int32_t c1);
 int adn_thin_wgrad(const float* thin, int32_t ct_n, const void* plain0, int32_t c0, const void* plain1,
                    int32_t c1, int32_t B, int32_t Hs, int32_t Ws, float* dw, void* workspace,
                    int64_t workspace_bytes, void* stream);
+int adn_thin_wgrad_ex(const float* thin, int32_t ct_n, const void* plain0, int32_t c0, const void* plain1,
+                      int32_t c1, int32_t B, int32_t Hs, int32_t Ws, float* dw, void* workspace,
+                      int64_t workspace_bytes, int32_t relu_plain0, void* stream);
 /* sum over n f32/dtype elements into one f32 (bias gradient of the outermost ConvTranspose2d). */
 int adn_sum_to_scalar(const void* x, int64_t n, int32_t dtype, float* out, void* workspace,
                       int64_t workspace_bytes, void* stream);

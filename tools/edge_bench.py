@@ -51,21 +51,36 @@ def main():
     out = torch.empty(B, 2 * Hs, 2 * Hs, device=DEV)
     bias = torch.zeros(1, device=DEV)
     px = B * Hs * Hs
+    def two_launch(fn):
+        def run():
+            os.environ['ADN_CONVT_N1_FUSED'] = '0'
+            try:
+                fn()
+            finally:
+                del os.environ['ADN_CONVT_N1_FUSED']
+        return run
+
+    n1 = lambda relu: K.convt_n1_forward(BF, B, Hs, Hs, ad if relu else rd, ru, wd, bias, 0, out, ws, relu_in0=relu)
+    n1_bytes = px * 128 * 2 + out.numel() * 4
     cases = [
-        ('l0_forward', lambda: K.l0_forward(x, w0, B, Hs, Hs, 0.2, ad, rd), px * 64 * 2 * 2 + x.numel() * 4),
-        ('l0_forward_1out', lambda: K.l0_forward(x, w0, B, Hs, Hs, 0.2, None, rd), px * 64 * 2 + x.numel() * 4),
-        ('d0_dgrad', lambda: K.d0_dgrad(dz, wd, B, Hs, Hs, K.Seg(64, out0=Gd, ref=rd, slope=0.0),
+        # the step writes ONE copy of the outermost activation (the leaky one, l0_forward_1out); its readers clamp it
+        ('l0_forward_1out', lambda: K.l0_forward(x, w0, B, Hs, Hs, 0.2, ad, None), px * 64 * 2 + x.numel() * 4),
+        ('l0_forward_2out', lambda: K.l0_forward(x, w0, B, Hs, Hs, 0.2, ad, rd), px * 64 * 2 * 2 + x.numel() * 4),
+        ('d0_dgrad', lambda: K.d0_dgrad(dz, wd, B, Hs, Hs, K.Seg(64, out0=Gd, ref=ad, slope=0.0),
                                         K.Seg(64, out0=Gu, ref=ru, slope=0.0, z=zu, mean=mean, istd=istd, partials=part)),
          px * 64 * 2 * 5 + dz.numel() * 4),
+        ('d0_wgrad_clamp', lambda: K.thin_wgrad(dz, ad, ru, B, Hs, Hs, dwd, ws, relu_plain0=True), px * 128 * 2 + dz.numel() * 4),
         ('d0_wgrad', lambda: K.thin_wgrad(dz, rd, ru, B, Hs, Hs, dwd, ws), px * 128 * 2 + dz.numel() * 4),
         ('l0_wgrad', lambda: K.thin_wgrad(x, Gd, None, B, Hs, Hs, dw0, ws), px * 64 * 2 + x.numel() * 4),
-        ('convt_n1_fwd', lambda: K.convt_n1_forward(BF, B, Hs, Hs, rd, ru, wd, bias, 0, out, ws), px * 128 * 2 + out.numel() * 4),
+        ('convt_n1_fwd_clamp', lambda: n1(True), n1_bytes),
+        ('convt_n1_fwd', lambda: n1(False), n1_bytes),
+        ('convt_n1_2launch', two_launch(lambda: n1(False)), n1_bytes + px * 64 * 2),
     ]
     for name, fn, byts in cases:
         if args.only and args.only not in name:
             continue
         t = timeit(fn, args.iters)
-        print(f'{name:18s} {t * 1e6:8.1f} us  {byts / t / 1e12:6.2f} TB/s (algorithmic bytes)', flush=True)
+        print(f'{name:20s} {t * 1e6:8.1f} us  {byts / t / 1e12:6.2f} TB/s (algorithmic bytes)', flush=True)
 
 
 if __name__ == '__main__':
