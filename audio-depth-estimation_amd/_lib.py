@@ -92,6 +92,7 @@ _PROTOS = {
     'adn_debug_stream_rmw': (C.c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p]),
     'adn_igemm_num_partials': (c_int64, [C.POINTER(AdnIgemmDesc)]),
     'adn_igemm_workspace_bytes': (c_int64, [C.POINTER(AdnIgemmDesc)]),
+    'adn_igemm_describe': (C.c_int, [C.POINTER(AdnIgemmDesc), C.c_char_p, C.c_int]),
     'adn_igemm': (C.c_int, [C.POINTER(AdnIgemmDesc), c_void_p]),
     'adn_wgrad_workspace_bytes': (c_int64, [C.POINTER(AdnWgradDesc)]),
     'adn_wgrad': (C.c_int, [C.POINTER(AdnWgradDesc), c_void_p]),

@@ -13,6 +13,7 @@
 // split-K into f32 slabs + a reduce pass.  The epilogue goes through LDS so that every global
 // access of the epilogue is a 16-byte, row-contiguous access.
 #include <stdarg.h>
+#include <stdio.h>
 #include <stdlib.h>
 
 #include <mutex>
@@ -52,8 +53,8 @@ const Tune& tune() {
     if (const char* e = getenv("ADN_IGEMM_RING_SCHED")) t.ring_sched = atoi(e);
     if (const char* e = getenv("ADN_IGEMM_RING_EPI")) t.ring_epi = atoi(e);      // A/B: ring kernel only for this epilogue (1 | 3)
     if (const char* e = getenv("ADN_IGEMM_RING_GEOM")) t.ring_geom = atoi(e);    // A/B: ring kernel only for this geometry (0 | 1)
-    if (const char* e = getenv("ADN_IGEMM_RING_HS")) t.ring_hs = atoi(e);
-    if (const char* e = getenv("ADN_IGEMM_RING_N64")) t.ring64n = atoi(e);       // A/B: 64-column layers on the ring kernel too        // A/B: ring kernel only at this small-grid height
+    if (const char* e = getenv("ADN_IGEMM_RING_HS")) t.ring_hs = atoi(e);        // A/B: ring kernel only at this small-grid height
+    if (const char* e = getenv("ADN_IGEMM_RING_N64")) t.ring64n = atoi(e);       // A/B: 64-column layers on the ring kernel too
   });
   return t;
 }
@@ -62,11 +63,10 @@ struct KParams {
   const void* in0;
   const void* in1;
   const void* w;
-  int B, Hs, Ws, C0, C1, N;
+  int Hs, Ws, C0, C1, N;
   int ks;         // S1 geometry: kernel side (1 or 3)
   int wstride;    // elements per packed-weight row (taps*Cin rounded up to the K-step)
   int Msmall;     // B*Hs*Ws
-  int kpt;        // K-steps per tap
   int ksteps;     // total K-steps
   int nsplit;     // split-K factor (grid.z)
   int tiles_m, tiles_n;
@@ -97,21 +97,197 @@ __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
 }
 
+// ---- LDS tile epilogue shared by the tile and the patch kernel ----
+// The BM x BN f32 accumulator tile goes through LDS (ctile[BM][LDC]) so that every global access of the epilogue is a
+// 16-byte, row-contiguous access: thread -> 8-channel column group cg = tid % CPR of the rows rsub + RSTEP * k.
+template <int BM, int BN, int NWN, int NTHR>
+struct TileEpi {
+  static constexpr int NW = NTHR / 64;      // waves (BM/64 x NWN, each owns a 64 x BN/NWN sub-tile)
+  static constexpr int WN = BN / NWN;       // wave tile columns
+  static constexpr int NT = WN / 16, MT = 4;
+  static constexpr int CPR = BN / 8;        // 8-channel column groups per row
+  static constexpr int RSTEP = NTHR / CPR;  // rows covered per pass
+  static constexpr int RPT = BM / RSTEP;    // rows per thread
+  static constexpr int LDC = BN + 4;        // epilogue tile leading dimension (floats)
+  static constexpr int lds_bytes = BM * LDC * 4;      // (the column-sum scratch [NW][2][BN] reuses the tile)
+};
+// Which BWD operand chunks are requested ahead of the K loop: none / activation reference, running gradient and raw conv
+// output / the same without the running-gradient chunk (read in the epilogue if a caller accumulates)
+enum class EpiPre { None, All, NoOld };
+template <int RPT, EpiPre PRE>
+struct EpiPreRegs {
+  u32x4_t r[PRE == EpiPre::None ? 1 : RPT], o[PRE == EpiPre::All ? RPT : 1], z[PRE == EpiPre::None ? 1 : RPT];
+};
+
+// ---- BWD epilogue operands requested up front (bf16, unsplit) ----
+// The BWD epilogue reads up to three tensors per output element (activation sign reference, the running gradient it
+// accumulates into, the raw conv output for the BatchNorm-backward sums): issued behind the K loop they are a fully
+// exposed HBM round trip per tile (the two workgroups of a CU run in phase: L2 dgrad 50 us with a store-only epilogue,
+// 85 us with this one).  Their addresses do not depend on the GEMM result, so the 16-byte chunks of this thread's
+// epilogue rows are loaded NOW and ride in registers under the K loop (<= 96 VGPRs; the kernels run 2 waves per SIMD).
+// row_op(row, op) -> the tile row is inside M; op = its output pixel.
+template <int BM, int BN, int NWN, int NTHR, EpiPre PRE, typename RowOp>
+__device__ __forceinline__ void tile_epi_prefetch(const KParams& p, int tile_n, RowOp row_op,
+                                                  EpiPreRegs<TileEpi<BM, BN, NWN, NTHR>::RPT, PRE>& pre) {
+  using E = TileEpi<BM, BN, NWN, NTHR>;
+  if constexpr (PRE != EpiPre::None) {
+    const int tid = threadIdx.x;
+    const int n0 = tile_n * BN + (tid % E::CPR) * 8, rsub = tid / E::CPR;
+    const bool first = n0 < p.seg[0].channels;
+    const AdnEpiSeg& sq = first ? p.seg[0] : p.seg[1];
+    const int nl0 = first ? n0 : n0 - p.seg[0].channels;
+#pragma unroll
+    for (int k = 0; k < E::RPT; ++k) {
+      pre.r[k] = pre.z[k] = u32x4_t{0u, 0u, 0u, 0u};
+      if constexpr (PRE == EpiPre::All) pre.o[k] = u32x4_t{0u, 0u, 0u, 0u};
+      int64_t op;
+      if (row_op(rsub + E::RSTEP * k, op)) {
+        const int64_t idx = op * sq.channels + nl0;
+        pre.r[k] = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const uint16_t*>(sq.ref) + idx);
+        if constexpr (PRE == EpiPre::All) {
+          if (sq.accumulate) pre.o[k] = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const uint16_t*>(sq.out0) + idx);
+        }
+        if (sq.partials) pre.z[k] = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const uint16_t*>(sq.z) + idx);
+      }
+    }
+  }
+}
+
+// Accumulators -> ctile -> the epilogue of every row of the tile -> column sums of the stats epilogues into partial row
+// `prow`.  slab != nullptr: split-K, the tile goes raw (f32) into this split's slab instead; the reduce kernel runs the epilogue.
+template <typename T, int BM, int BN, int NWN, int NTHR, EpiPre PRE, typename RowOp>
+__device__ __forceinline__ void tile_epi_finish(char* smem, const KParams& p, const f32x4_t (&acc)[4][BN / NWN / 16], int tile_n,
+                                                int64_t prow, RowOp row_op, float* slab, bool pre_on,
+                                                const EpiPreRegs<TileEpi<BM, BN, NWN, NTHR>::RPT, PRE>& pre) {
+  using E = TileEpi<BM, BN, NWN, NTHR>;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave / NWN, wn = wave % NWN;
+  const int frow = lane & 15, fq = lane >> 4;
+  __syncthreads();   // all waves done with the staging buffers before the epilogue tile reuses them
+  float* ct = reinterpret_cast<float*>(smem);
+#pragma unroll
+  for (int i = 0; i < E::MT; ++i)
+#pragma unroll
+    for (int j = 0; j < E::NT; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        ct[(wm * 64 + i * 16 + 4 * fq + r) * E::LDC + wn * E::WN + j * 16 + frow] = acc[i][j][r];
+  __syncthreads();
+
+  const int cg = tid % E::CPR, rsub = tid / E::CPR;
+  const int n0 = tile_n * BN + cg * 8;
+  int epi = p.epi;
+  AdnEpiSeg sg;
+  int nl;
+  if (slab != nullptr) {
+    epi = ADN_EPI_RAW;
+    sg = p.seg[0];
+    sg.out0 = slab;
+    sg.channels = p.N;
+    sg.partials = nullptr;
+    nl = n0;
+  } else if (n0 < p.seg[0].channels) {
+    sg = p.seg[0];
+    nl = n0;
+  } else {
+    sg = p.seg[1];
+    nl = n0 - p.seg[0].channels;
+  }
+  EpiCols cols;
+  epi_cols_init<T>(epi, sg, nl, cols);
+  float s1[8], s2[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) s1[e] = s2[e] = 0.f;
+
+#pragma unroll
+  for (int k = 0; k < E::RPT; ++k) {
+    const int row = rsub + E::RSTEP * k;
+    int64_t op;
+    if (!row_op(row, op)) continue;
+    float v[8];
+    const f32x4_t v0 = *reinterpret_cast<const f32x4_t*>(ct + row * E::LDC + cg * 8);
+    const f32x4_t v1 = *reinterpret_cast<const f32x4_t*>(ct + row * E::LDC + cg * 8 + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[e] = v0[e];
+      v[4 + e] = v1[e];
+    }
+    if constexpr (PRE != EpiPre::None) {
+      if (pre_on) {
+        if constexpr (PRE == EpiPre::NoOld) {
+          u32x4_t old = {0u, 0u, 0u, 0u};
+          if (sg.accumulate) old = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const uint16_t*>(sg.out0) + op * sg.channels + nl);
+          epi_bwd_pre8(sg, cols, op, nl, v, pre.r[k], old, pre.z[k], s1, s2);
+        } else {
+          epi_bwd_pre8(sg, cols, op, nl, v, pre.r[k], pre.o[k], pre.z[k], s1, s2);
+        }
+        continue;
+      }
+    }
+    epi_vec8<T>(epi, sg, cols, op, nl, v, s1, s2);
+  }
+
+  // (workgroup-uniform condition: a 128-wide tile may straddle a segment with stats and one without; split-K: epi is RAW)
+  if ((p.seg[0].partials != nullptr || p.seg[1].partials != nullptr) && (epi == ADN_EPI_Z_STATS || epi == ADN_EPI_BWD)) {
+    // reduce over the row subsets: lanes sharing cg inside a wave, then the NW waves through LDS.
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+#pragma unroll
+      for (int o = E::CPR; o < 64; o <<= 1) {
+        s1[e] += __shfl_xor(s1[e], o, 64);
+        s2[e] += __shfl_xor(s2[e], o, 64);
+      }
+    }
+    __syncthreads();  // everyone is done reading ctile
+    float* red = reinterpret_cast<float*>(smem);  // [NW waves][2][BN]
+    if (lane < E::CPR) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        red[(wave * 2 + 0) * BN + cg * 8 + e] = s1[e];
+        red[(wave * 2 + 1) * BN + cg * 8 + e] = s2[e];
+      }
+    }
+    __syncthreads();
+    if (tid < 2 * BN) {
+      const int st = tid / BN, c = tid % BN;
+      float t = 0.f;
+#pragma unroll
+      for (int w = 0; w < E::NW; ++w) t += red[(w * 2 + st) * BN + c];
+      const int n = tile_n * BN + c;
+      const AdnEpiSeg& sq = (n < p.seg[0].channels) ? p.seg[0] : p.seg[1];
+      const int ncl = (n < p.seg[0].channels) ? n : n - p.seg[0].channels;
+      if (sq.partials) sq.partials[(prow * 2 + st) * sq.channels + ncl] = t;
+    }
+  }
+}
+
+// LDS budget of a kernel instantiation: the one source for the kernel body and its launcher
+constexpr int LDS_MAX = 160 * 1024;
+template <int BM, int BN, int NWN>
+struct TileCfg {
+  static constexpr int NTHR = BM * NWN;            // 64 threads per 64 x (BN/NWN) wave tile
+  static constexpr int STAGES = (BM == 256 && NWN == 2) ? 3 : 2;
+  static constexpr int STAGE_BYTES = (BM + BN) * 128;          // a K-step (128 bytes of K) of both operands
+  using Epi = TileEpi<BM, BN, NWN, NTHR>;
+  static constexpr int lds_bytes = STAGES * STAGE_BYTES > Epi::lds_bytes ? STAGES * STAGE_BYTES : Epi::lds_bytes;
+  static_assert(lds_bytes <= LDS_MAX, "tile kernel: LDS budget");
+};
+
 // Tile configurations (waves are BM/64 x NWN, each wave owns a 64 x BN/NWN sub-tile):
 //   128 x 128, 2x2 waves, 2 LDS stages, 2 workgroups per CU   small-M / split-K / short-K layers
 //   128 x  64, 2x2 waves, 2 stages                             narrow N with small M
 //   256 x  64, 4x1 waves, 2 stages, 2 workgroups per CU        N = 64: every wave keeps a 64x64 sub-tile
 //   256 x 128, 4x2 waves, 3 stages, 1 workgroup per CU         long K: the DMA of steps s+1 and s+2 stays in
 //             flight across the per-step barrier (counted s_waitcnt vmcnt, raw s_barrier)
-// (PRE = false, an instantiation without the backward-epilogue prefetch registers for forward / split-K launches, was timed
-//  in round 3 on the small-image layers: L5 / L6 / D5 forward 20.7 / 16.6 / 32.3 -> 19.9 / 15.7 / 31.4 us, the rest +-1 %:
-//  inside the noise, so the template parameter stays but only PRE = true is instantiated)
-template <typename T, int BM, int BN, int NWN, int GEOM, bool WIDE, bool PRE = true>
+// (An instantiation without the backward-epilogue prefetch registers for forward / split-K launches was timed in round 3 on
+//  the small-image layers: L5 / L6 / D5 forward 20.7 / 16.6 / 32.3 -> 19.9 / 15.7 / 31.4 us, the rest +-1 %: inside the
+//  noise, so every bf16 instantiation carries them)
+template <typename T, int BM, int BN, int NWN, int GEOM, bool WIDE>
 __global__ __launch_bounds__(BM * NWN, 2) void igemm_mfma_kernel(KParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)   // buffer-resource builtins exist only in the device pass; the host needs the stub only
-  constexpr int NTHR = BM * NWN;            // 64 threads per 64 x (BN/NWN) wave tile
-  constexpr int NW = NTHR / 64;
-  constexpr int STAGES = (BM == 256 && NWN == 2) ? 3 : 2;
+  using Cfg = TileCfg<BM, BN, NWN>;
+  constexpr int NTHR = Cfg::NTHR, STAGES = Cfg::STAGES, STAGE_BYTES = Cfg::STAGE_BYTES;
   constexpr int EPC = 16 / (int)sizeof(T);  // elements per 16-byte chunk
   constexpr int BK = 8 * EPC;               // elements per K-step (128 bytes)
   constexpr int WN = BN / NWN;              // wave tile columns
@@ -121,8 +297,6 @@ __global__ __launch_bounds__(BM * NWN, 2) void igemm_mfma_kernel(KParams p) {
   constexpr int APASS = BM / RPASS;         // = 4
   constexpr int BPASS = BN / RPASS;
   constexpr int LOADS = APASS + BPASS;      // LDS-DMA instructions per wave per stage
-  constexpr int STAGE_BYTES = (BM + BN) * 128;
-  constexpr int LDC = BN + 4;               // epilogue tile leading dimension (floats)
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x;
@@ -312,47 +486,24 @@ __global__ __launch_bounds__(BM * NWN, 2) void igemm_mfma_kernel(KParams p) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-  // ---- BWD epilogue operands requested up front (bf16, unsplit) ----
-  // The BWD epilogue reads up to three tensors per output element (activation sign reference, the running gradient it
-  // accumulates into, the raw conv output for the BatchNorm-backward sums): issued behind the K loop they are a fully
-  // exposed HBM round trip per tile (the two workgroups of a CU run in phase: L2 dgrad 50 us with a store-only epilogue,
-  // 85 us with this one).  Their addresses do not depend on the GEMM result, so the 16-byte chunks of this thread's
-  // epilogue rows are loaded NOW and ride in registers under the K loop (<= 96 VGPRs; the kernel runs 2 waves per SIMD).
-  constexpr int CPR = BN / 8;        // 8-channel column groups per row
-  constexpr int RSTEP = NTHR / CPR;  // rows covered per pass
-  constexpr int RPT = BM / RSTEP;    // rows per thread
-  const int e_cg = tid % CPR;
-  const int e_rsub = tid / CPR;
-  const int e_n0 = tile_n * BN + e_cg * 8;
-  constexpr bool PRE_OK = PRE && sizeof(T) == 2;
-  const bool pre_on = PRE_OK && p.epi == ADN_EPI_BWD && p.nsplit == 1;
-  u32x4_t pre_r[RPT], pre_o[RPT], pre_z[RPT];
-  if constexpr (PRE_OK) {
-    if (pre_on) {
-      const bool first = e_n0 < p.seg[0].channels;
-      const AdnEpiSeg& sq = first ? p.seg[0] : p.seg[1];
-      const int nl0 = first ? e_n0 : e_n0 - p.seg[0].channels;
-#pragma unroll
-      for (int k = 0; k < RPT; ++k) {
-        const int m = tile_m * BM + e_rsub + RSTEP * k;
-        pre_r[k] = pre_o[k] = pre_z[k] = u32x4_t{0u, 0u, 0u, 0u};
-        if (m < p.Msmall) {
-          int64_t op;
-          if constexpr (GEOM != ADN_GEMM_T2) {
-            op = m;
-          } else {
-            int b, i, jx;
-            decode(m, b, i, jx);
-            op = ((int64_t)b * Hl + 2 * i + ph) * Wl + 2 * jx + pw;
-          }
-          const int64_t idx = op * sq.channels + nl0;
-          pre_r[k] = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const uint16_t*>(sq.ref) + idx);
-          if (sq.accumulate) pre_o[k] = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const uint16_t*>(sq.out0) + idx);
-          if (sq.partials) pre_z[k] = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const uint16_t*>(sq.z) + idx);
-        }
-      }
+  // ---- BWD epilogue operands requested up front (bf16, unsplit; see tile_epi_prefetch) ----
+  // tile row -> (inside M, output pixel)
+  auto row_op = [&](int row, int64_t& op) -> bool {
+    const int m = tile_m * BM + row;
+    if (m >= p.Msmall) return false;
+    if constexpr (GEOM != ADN_GEMM_T2) {
+      op = m;
+    } else {
+      int b, i, jx;
+      decode(m, b, i, jx);
+      op = ((int64_t)b * Hl + 2 * i + ph) * Wl + 2 * jx + pw;
     }
-  }
+    return true;
+  };
+  constexpr EpiPre PRE = sizeof(T) == 2 ? EpiPre::All : EpiPre::None;
+  const bool pre_on = PRE != EpiPre::None && p.epi == ADN_EPI_BWD && p.nsplit == 1;
+  EpiPreRegs<Cfg::Epi::RPT, PRE> pre;
+  if (pre_on) tile_epi_prefetch<BM, BN, NWN, NTHR, PRE>(p, tile_n, row_op, pre);
 
   // ---- pipeline: STAGES-1 steps of LDS-DMA in flight; one raw barrier per K-step ----
   // At the top of step s the stages s .. s+STAGES-2 have been issued.  "s_waitcnt vmcnt(LOADS*(STAGES-2))"
@@ -396,112 +547,10 @@ __global__ __launch_bounds__(BM * NWN, 2) void igemm_mfma_kernel(KParams p) {
     }
     cur = cur + 1 == STAGES ? 0 : cur + 1;
   }
-  __syncthreads();   // all waves done with the staging buffers before the epilogue tile reuses them
-
-  // ---- epilogue through LDS: ctile[BM][LDC] f32 ----
-  float* ct = reinterpret_cast<float*>(smem);
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        ct[(wm * 64 + i * 16 + 4 * fq + r) * LDC + wn * WN + j * 16 + frow] = acc[i][j][r];
-  __syncthreads();
-
-  const int cg = e_cg;
-  const int rsub = e_rsub;
-  const int n0 = e_n0;
-
-  int epi = p.epi;
-  AdnEpiSeg sg;
-  int nl;
-  int64_t mout_total = (GEOM == ADN_GEMM_T2) ? (int64_t)p.Msmall * 4 : (int64_t)p.Msmall;
-  if (p.nsplit > 1) {
-    epi = ADN_EPI_RAW;
-    sg = p.seg[0];
-    sg.out0 = p.slab + (int64_t)split * mout_total * p.N;
-    sg.channels = p.N;
-    sg.partials = nullptr;
-    nl = n0;
-  } else if (n0 < p.seg[0].channels) {
-    sg = p.seg[0];
-    nl = n0;
-  } else {
-    sg = p.seg[1];
-    nl = n0 - p.seg[0].channels;
-  }
-  EpiCols cols;
-  epi_cols_init<T>(epi, sg, nl, cols);
-  float s1[8], s2[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) s1[e] = s2[e] = 0.f;
-
-#pragma unroll
-  for (int k = 0; k < RPT; ++k) {
-    const int row = rsub + RSTEP * k;
-    const int m = tile_m * BM + row;
-    if (m < p.Msmall) {
-      int64_t op;
-      if constexpr (GEOM != ADN_GEMM_T2) {
-        op = m;
-      } else {
-        int b, i, jx;
-        decode(m, b, i, jx);
-        op = ((int64_t)b * Hl + 2 * i + ph) * Wl + 2 * jx + pw;
-      }
-      float v[8];
-      const f32x4_t v0 = *reinterpret_cast<const f32x4_t*>(ct + row * LDC + cg * 8);
-      const f32x4_t v1 = *reinterpret_cast<const f32x4_t*>(ct + row * LDC + cg * 8 + 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v[e] = v0[e];
-        v[4 + e] = v1[e];
-      }
-      if constexpr (PRE_OK) {
-        if (pre_on) {
-          epi_bwd_pre8(sg, cols, op, nl, v, pre_r[k], pre_o[k], pre_z[k], s1, s2);
-          continue;
-        }
-      }
-      epi_vec8<T>(epi, sg, cols, op, nl, v, s1, s2);
-    }
-  }
-
-  // (workgroup-uniform condition: a 128-wide tile may straddle a segment with stats and one without)
-  if (p.nsplit == 1 && (p.seg[0].partials != nullptr || p.seg[1].partials != nullptr) &&
-      (p.epi == ADN_EPI_Z_STATS || p.epi == ADN_EPI_BWD)) {
-    // reduce over the row subsets: lanes sharing cg inside a wave, then the NW waves through LDS.
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-#pragma unroll
-      for (int o = CPR; o < 64; o <<= 1) {
-        s1[e] += __shfl_xor(s1[e], o, 64);
-        s2[e] += __shfl_xor(s2[e], o, 64);
-      }
-    }
-    __syncthreads();  // everyone is done reading ctile
-    float* red = reinterpret_cast<float*>(smem);  // [NW waves][2][BN]
-    if (lane < CPR) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        red[(wave * 2 + 0) * BN + cg * 8 + e] = s1[e];
-        red[(wave * 2 + 1) * BN + cg * 8 + e] = s2[e];
-      }
-    }
-    __syncthreads();
-    if (tid < 2 * BN) {
-      const int st = tid / BN, c = tid % BN;
-      float t = 0.f;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) t += red[(w * 2 + st) * BN + c];
-      const int n = tile_n * BN + c;
-      const AdnEpiSeg& sq = (n < p.seg[0].channels) ? p.seg[0] : p.seg[1];
-      const int ncl = (n < p.seg[0].channels) ? n : n - p.seg[0].channels;
-      const int64_t P = (int64_t)phase * p.tiles_m + tile_m;
-      if (sq.partials) sq.partials[(P * 2 + st) * sq.channels + ncl] = t;
-    }
-  }
+  // ---- epilogue through LDS; split-K: raw into this split's slab ----
+  const int64_t mout_total = (GEOM == ADN_GEMM_T2) ? (int64_t)p.Msmall * 4 : (int64_t)p.Msmall;
+  float* slab = p.nsplit > 1 ? p.slab + (int64_t)split * mout_total * p.N : nullptr;
+  tile_epi_finish<T, BM, BN, NWN, NTHR, PRE>(smem, p, acc, tile_n, (int64_t)phase * p.tiles_m + tile_m, row_op, slab, pre_on, pre);
 #endif
 }
 
@@ -533,25 +582,36 @@ __global__ __launch_bounds__(BM * NWN, 2) void igemm_mfma_kernel(KParams p) {
 // PAIR (S2 / T2, 8 x 8 small-grid images -- the Hs = 8 level of unet_256): a tile is two whole images side by side (8 rows x
 // [8 columns of image 2t | 8 columns of image 2t + 1]); every patch plane holds the two images' 9 columns back to back (18
 // columns), so the only change for the fragment reads is +1 LDS pixel for the second image's output columns.
+template <int BN, int GEOM, bool TALL, bool PAIR>
+struct PatchCfg {
+  static constexpr bool S2 = GEOM == ADN_GEMM_S2, S1 = GEOM == ADN_GEMM_S1;
+  static constexpr int TH = TALL ? 16 : 8, TW = 16;
+  static constexpr int BM = TH * TW, NWN = TALL ? 1 : 2, NTHR = 256;
+  static constexpr int MW = (S1 || PAIR) ? TW + 2 : TW + 1;   // patch columns per plane (S1: 3 x 3 window, 18 columns; PAIR: 9 + 9)
+  static constexpr int SEG_PIX = S2 ? 2 * (TH + 1) * MW : (S1 ? (TH + 2) * MW : (TH + 1) * MW);   // 306 / 180 / 153 pixels
+  static constexpr int TPS = S1 ? 3 : 2;                      // taps per K-step (S1: one kernel row)
+  static constexpr int PPIECES = (SEG_PIX + 15) / 16;         // 1-KiB DMA pieces per segment (20 / 12 / 10)
+  static constexpr int PBUF = PPIECES * 1024;                 // one patch segment
+  static constexpr int BBUF = TPS * BN * 64;                  // one weight stage: [TPS taps][BN][64 B]
+  using Epi = TileEpi<BM, BN, NWN, NTHR>;
+  static constexpr int stage_bytes = 2 * PBUF + 2 * BBUF;     // patch segments and weight stages are double-buffered
+  static constexpr int lds_bytes = stage_bytes > Epi::lds_bytes ? stage_bytes : Epi::lds_bytes;
+  static_assert(lds_bytes <= LDS_MAX, "patch kernel: LDS budget");
+};
+
 template <int BN, int GEOM, bool TALL = false, bool PRE = true, bool PAIR = false>
 __global__ __launch_bounds__(256, 2) void igemm_patch_kernel(KParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef uint16_t T;
-  constexpr int TH = TALL ? 16 : 8, TW = 16;
-  constexpr int BM = TH * TW, NWN = TALL ? 1 : 2, NTHR = 256;
+  using Cfg = PatchCfg<BN, GEOM, TALL, PAIR>;
+  constexpr int TH = Cfg::TH, TW = Cfg::TW, BM = Cfg::BM, NWN = Cfg::NWN, NTHR = Cfg::NTHR;
   constexpr int WN = BN / NWN, NT = WN / 16, MT = 4;
-  constexpr bool S2 = GEOM == ADN_GEMM_S2, S1 = GEOM == ADN_GEMM_S1;
-  constexpr int MW = (S1 || PAIR) ? TW + 2 : TW + 1;          // patch columns per plane (S1: 3 x 3 window, 18 columns; PAIR: 9 + 9)
-  constexpr int SEG_PIX = S2 ? 2 * (TH + 1) * MW : (S1 ? (TH + 2) * MW : (TH + 1) * MW);   // 306 / 180 / 153 pixels
+  constexpr bool S2 = Cfg::S2, S1 = Cfg::S1;
+  constexpr int MW = Cfg::MW, SEG_PIX = Cfg::SEG_PIX, TPS = Cfg::TPS, PPIECES = Cfg::PPIECES, PBUF = Cfg::PBUF, BBUF = Cfg::BBUF;
   constexpr int SEG_STEPS = S2 ? 4 : (S1 ? 3 : 2);            // K-steps served by one segment
-  constexpr int TPS = S1 ? 3 : 2;                             // taps per K-step (S1: one kernel row)
-  constexpr int PPIECES = (SEG_PIX + 15) / 16;                // 1-KiB DMA pieces per segment (20 / 12 / 10)
   constexpr int PK = (PPIECES + 3) / 4;                       // pieces per wave (5 / 3 / 3)
-  constexpr int PBUF = PPIECES * 1024;
   constexpr int BPT = BN / 16;                                // weight pieces per tap
   constexpr int BK_ = TPS * BPT / 4;                          // weight pieces per wave and step (4 / 2, S1: 6 / 3)
-  constexpr int BBUF = TPS * BN * 64;                         // one weight stage: [TPS taps][BN][64 B]
-  constexpr int LDC = BN + 4;
   constexpr unsigned OOB = 0x80000000u;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Pl = smem;                       // [2][PBUF]
@@ -693,40 +753,23 @@ __global__ __launch_bounds__(256, 2) void igemm_patch_kernel(KParams p) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-  // ---- BWD epilogue operands requested up front (see the kernel above) ----
-  constexpr int CPR = BN / 8, RSTEP = NTHR / CPR, RPT = BM / RSTEP;
-  const int e_cg = tid % CPR, e_rsub = tid / CPR;
-  const int e_n0 = tile_n * BN + e_cg * 8;
-  auto row_op = [&](int row) -> int64_t {       // output pixel index of tile row `row` (row = oyl * 16 + oxl)
+  // ---- BWD epilogue operands requested up front (see tile_epi_prefetch) ----
+  auto row_op = [&](int row, int64_t& op) -> bool {       // output pixel index of tile row `row` (row = oyl * 16 + oxl)
     const int oy = oy0 + (row >> 4);
     const int ox = PAIR ? (row & 7) : ox0 + (row & 15);
     const int ib = PAIR ? tb + ((row >> 3) & 1) : tb;
-    if constexpr (S2 || S1) return ((int64_t)ib * Hs + oy) * Ws + ox;
-    else return ((int64_t)ib * Hl + 2 * oy + ph) * Wl + 2 * ox + pw;
+    if constexpr (S2 || S1) op = ((int64_t)ib * Hs + oy) * Ws + ox;
+    else op = ((int64_t)ib * Hl + 2 * oy + ph) * Wl + 2 * ox + pw;
+    return true;                                          // (the images tile exactly: no row beyond M)
   };
   // (S2 = dgrad of a transposed conv never accumulates in the U-Net: its running-gradient chunk is not kept in registers
-  //  -- 32 VGPRs that made the 128-column variant spill -- but read in the epilogue if a caller asks for it)
-  constexpr bool KEEP_OLD = !(S2 || S1);      // T2 (dgrad of the strided conv) is the accumulating one in the U-Net
-  constexpr int NPO = KEEP_OLD ? RPT : 1;
+  //  -- 32 VGPRs that made the 128-column variant spill -- but read in the epilogue if a caller asks for it;
+  //  T2 (dgrad of the strided conv) is the accumulating one in the U-Net)
   // (PRE = false: the TALL forward instantiation -- without the 8 x 2 prefetch registers it keeps 3 waves per SIMD)
+  constexpr EpiPre EPRE = !PRE ? EpiPre::None : ((S2 || S1) ? EpiPre::NoOld : EpiPre::All);
   const bool pre_on = PRE && p.epi == ADN_EPI_BWD;
-  u32x4_t pre_r[RPT], pre_o[NPO], pre_z[RPT];
-  if (pre_on) {
-    const bool first = e_n0 < p.seg[0].channels;
-    const AdnEpiSeg& sq = first ? p.seg[0] : p.seg[1];
-    const int nl0 = first ? e_n0 : e_n0 - p.seg[0].channels;
-#pragma unroll
-    for (int k = 0; k < RPT; ++k) {
-      const int64_t idx = row_op(e_rsub + RSTEP * k) * sq.channels + nl0;
-      pre_r[k] = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const uint16_t*>(sq.ref) + idx);
-      pre_z[k] = u32x4_t{0u, 0u, 0u, 0u};
-      if constexpr (KEEP_OLD) {
-        pre_o[k] = u32x4_t{0u, 0u, 0u, 0u};
-        if (sq.accumulate) pre_o[k] = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const uint16_t*>(sq.out0) + idx);
-      }
-      if (sq.partials) pre_z[k] = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const uint16_t*>(sq.z) + idx);
-    }
-  }
+  EpiPreRegs<Cfg::Epi::RPT, EPRE> pre;
+  if (pre_on) tile_epi_prefetch<BM, BN, NWN, NTHR, EPRE>(p, tile_n, row_op, pre);
 
   // ---- prologue: the whole first patch segment + the weights of step 0 ----
 #pragma unroll
@@ -772,89 +815,8 @@ __global__ __launch_bounds__(256, 2) void igemm_patch_kernel(KParams p) {
       }
     }
   }
-  __syncthreads();
-
-  // ---- epilogue through LDS (as above; tile row = oyl * 16 + oxl) ----
-  float* ct = reinterpret_cast<float*>(smem);
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        ct[(wm * 64 + i * 16 + 4 * fq + r) * LDC + wn * WN + j * 16 + frow] = acc[i][j][r];
-  __syncthreads();
-  const int cg = e_cg, rsub = e_rsub, n0 = e_n0;
-  const int epi = p.epi;
-  AdnEpiSeg sg2;
-  int nl;
-  if (n0 < p.seg[0].channels) {
-    sg2 = p.seg[0];
-    nl = n0;
-  } else {
-    sg2 = p.seg[1];
-    nl = n0 - p.seg[0].channels;
-  }
-  EpiCols cols;
-  epi_cols_init<T>(epi, sg2, nl, cols);
-  float s1[8], s2[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) s1[e] = s2[e] = 0.f;
-#pragma unroll
-  for (int k = 0; k < RPT; ++k) {
-    const int row = rsub + RSTEP * k;
-    const int64_t op = row_op(row);
-    float v[8];
-    const f32x4_t v0 = *reinterpret_cast<const f32x4_t*>(ct + row * LDC + cg * 8);
-    const f32x4_t v1 = *reinterpret_cast<const f32x4_t*>(ct + row * LDC + cg * 8 + 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      v[e] = v0[e];
-      v[4 + e] = v1[e];
-    }
-    if (pre_on) {
-      if constexpr (!KEEP_OLD) {
-        u32x4_t old = {0u, 0u, 0u, 0u};
-        if (sg2.accumulate) old = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const uint16_t*>(sg2.out0) + op * sg2.channels + nl);
-        epi_bwd_pre8(sg2, cols, op, nl, v, pre_r[k], old, pre_z[k], s1, s2);
-      } else {
-        epi_bwd_pre8(sg2, cols, op, nl, v, pre_r[k], pre_o[k], pre_z[k], s1, s2);
-      }
-    } else {
-      epi_vec8<T>(epi, sg2, cols, op, nl, v, s1, s2);
-    }
-  }
-  if ((p.seg[0].partials != nullptr || p.seg[1].partials != nullptr) && (p.epi == ADN_EPI_Z_STATS || p.epi == ADN_EPI_BWD)) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-#pragma unroll
-      for (int o = CPR; o < 64; o <<= 1) {
-        s1[e] += __shfl_xor(s1[e], o, 64);
-        s2[e] += __shfl_xor(s2[e], o, 64);
-      }
-    }
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(smem);  // [4 waves][2][BN]
-    if (lane < CPR) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        red[(wave * 2 + 0) * BN + cg * 8 + e] = s1[e];
-        red[(wave * 2 + 1) * BN + cg * 8 + e] = s2[e];
-      }
-    }
-    __syncthreads();
-    if (tid < 2 * BN) {
-      const int st = tid / BN, c = tid % BN;
-      float t = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) t += red[(w * 2 + st) * BN + c];
-      const int n = tile_n * BN + c;
-      const AdnEpiSeg& sq = (n < p.seg[0].channels) ? p.seg[0] : p.seg[1];
-      const int ncl = (n < p.seg[0].channels) ? n : n - p.seg[0].channels;
-      const int64_t P = (int64_t)phase * p.tiles_m + tile_m;
-      if (sq.partials) sq.partials[(P * 2 + st) * sq.channels + ncl] = t;
-    }
-  }
+  // ---- epilogue through LDS (tile row = oyl * 16 + oxl) ----
+  tile_epi_finish<T, BM, BN, NWN, NTHR, EPRE>(smem, p, acc, tile_n, (int64_t)phase * p.tiles_m + tile_m, row_op, nullptr, pre_on, pre);
 #endif
 }
 
@@ -874,6 +836,10 @@ __global__ __launch_bounds__(256) void igemm_direct_kernel(KParams p) {
     const int64_t op = e / p.N;
     const int n = (int)(e - op * p.N);
     float acc = 0.f;
+    auto dot = [&](int64_t pix, const T* wr) {      // one tap: all gathered channels of input pixel `pix`
+      for (int c = 0; c < p.C0; ++c) acc += ElemTraits<T>::load(in0 + pix * p.C0 + c) * ElemTraits<T>::load(wr + c);
+      for (int c = 0; c < p.C1; ++c) acc += ElemTraits<T>::load(in1 + pix * p.C1 + c) * ElemTraits<T>::load(wr + p.C0 + c);
+    };
     if constexpr (GEOM == ADN_GEMM_S2) {
       const int b = (int)(op / (Hs * Ws));
       const int rem = (int)(op - (int64_t)b * (Hs * Ws));
@@ -883,9 +849,7 @@ __global__ __launch_bounds__(256) void igemm_direct_kernel(KParams p) {
         if ((unsigned)iy >= (unsigned)Hl || (unsigned)ix >= (unsigned)Wl) continue;
         const int64_t pix = ((int64_t)b * Hl + iy) * Wl + ix;
         const T* wr = w + (int64_t)n * p.wstride + tap * Cin;
-        for (int c = 0; c < p.C0; ++c) acc += ElemTraits<T>::load(in0 + pix * p.C0 + c) * ElemTraits<T>::load(wr + c);
-        for (int c = 0; c < p.C1; ++c)
-          acc += ElemTraits<T>::load(in1 + pix * p.C1 + c) * ElemTraits<T>::load(wr + p.C0 + c);
+        dot(pix, wr);
       }
     } else if constexpr (GEOM == ADN_GEMM_S1) {
       const int b = (int)(op / (Hs * Ws));
@@ -897,9 +861,7 @@ __global__ __launch_bounds__(256) void igemm_direct_kernel(KParams p) {
         if ((unsigned)iy >= (unsigned)Hs || (unsigned)ix >= (unsigned)Ws) continue;
         const int64_t pix = ((int64_t)b * Hs + iy) * Ws + ix;
         const T* wr = w + (int64_t)n * p.wstride + tap * Cin;
-        for (int c = 0; c < p.C0; ++c) acc += ElemTraits<T>::load(in0 + pix * p.C0 + c) * ElemTraits<T>::load(wr + c);
-        for (int c = 0; c < p.C1; ++c)
-          acc += ElemTraits<T>::load(in1 + pix * p.C1 + c) * ElemTraits<T>::load(wr + p.C0 + c);
+        dot(pix, wr);
       }
     } else {
       const int b = (int)(op / ((int64_t)Hl * Wl));
@@ -912,9 +874,7 @@ __global__ __launch_bounds__(256) void igemm_direct_kernel(KParams p) {
         if ((unsigned)iy >= (unsigned)Hs || (unsigned)ix >= (unsigned)Ws) continue;
         const int64_t pix = ((int64_t)b * Hs + iy) * Ws + ix;
         const T* wr = w + ((int64_t)phase * p.N + n) * p.wstride + t * Cin;
-        for (int c = 0; c < p.C0; ++c) acc += ElemTraits<T>::load(in0 + pix * p.C0 + c) * ElemTraits<T>::load(wr + c);
-        for (int c = 0; c < p.C1; ++c)
-          acc += ElemTraits<T>::load(in1 + pix * p.C1 + c) * ElemTraits<T>::load(wr + p.C0 + c);
+        dot(pix, wr);
       }
     }
     p.slab[e] = acc;
@@ -958,28 +918,100 @@ inline int reduce_rows(int64_t mout, int N) {
   return (int)rb;
 }
 
+// Which kernel runs a launch.  Tile: igemm_mfma_kernel (any aligned shape; split-K into f32 slabs + the reduce kernel when
+// there are too few tiles).  Patch: igemm_patch_kernel (bf16, wide, unsplit, image 8 x 16 tileable) in its plain, tall or
+// pair form.  Ring: igemm_ring_kernel (bf16, wide, unsplit, image 16 x 16 tileable, Z_STATS / BWD).  Direct: one thread per
+// output element + the reduce kernel for the epilogue (channel counts the MFMA loaders cannot address).
+enum class Kind { Direct, Tile, Patch, Ring };
+
 struct Plan {
-  bool mfma;
-  bool wide;
-  bool patch;       // patch-staged kernel (bf16, wide, unsplit, image 8 x 16 tileable)
-  bool tall;        // its 16 x 16-pixel, 4 x 1-wave form (64 output columns, T2 / S1, image 16 x 16 tileable)
-  bool pair;        // its two-images-per-tile form (S2 / T2, 8 x 8 small-grid images, 128 output columns, unsplit)
-  bool ring;        // ring-fed persistent kernel (igemm_ring.h): 16 x 16-pixel x bn tiles, one 8-wave workgroup per CU
+  Kind kind;
+  bool tall;        // Patch only: the 16 x 16-pixel, 4 x 1-wave form (64 output columns, T2 / S1, image 16 x 16 tileable)
+  bool pair;        // Patch only: the two-images-per-tile form (T2, 8 x 8 small-grid images, 128 output columns)
+  bool wide;        // every K-step lies inside one tap of one source (narrow: single source, several taps per K-step)
+  bool onepx;       // Tile only: 1 x 1 small-grid images, only the taps that can be in range are walked
   int wstride;
-  int rb;
-  int bm;
-  int bn;
+  int rb;           // rows per block of the reduce kernel (Direct, split-K)
+  int bm, bn;
   int nsplit;
   int tiles_m, tiles_n, phases;
-  int kpt, ksteps;
-  bool onepx;
+  int ksteps;
   int64_t mout;
   int64_t partial_rows;
   int64_t slab_bytes;
 };
 
-bool make_plan(const AdnIgemmDesc* d, Plan* pl) {
-  const int esz = d->dtype == ADN_BF16 ? 2 : 4;
+// Tile columns of the tile and patch kernels (segments are multiples of 64: an 8-channel group never straddles)
+int plan_columns(const AdnIgemmDesc* d, bool wide, int64_t msmall) {
+  const Tune& tn = tune();
+  if (tn.bn) return (tn.bn == 128 && d->N % 128 == 0) ? 128 : 64;
+  int bn = (d->N % 128 == 0) ? 128 : 64;
+  if (d->dtype != ADN_BF16) return bn;
+  // Transposed-conv geometry (forward of the up path, input gradients of the down path): 64-column tiles throughout --
+  // the tall 256 x 64 patch form on the 16 x 16 ... 64 x 64 image levels (less patch halo per pixel, half the weight bytes
+  // per K-step), twice the workgroups on the split-K levels.  Headline step 2.909 -> 2.860 ms and 2.932 -> 2.894 ms on two
+  // boxes (ADN_IGEMM_BN_T2=128 restores 128-column tiles for an A/B; the two-image PAIR form keeps its 128 columns).
+  if (d->geom == ADN_GEMM_T2) bn = (tn.bn_t2 == 128 && d->N % 128 == 0) ? 128 : 64;
+  const int64_t t128 = adn_cdiv(msmall, 128) * (d->N / 128);
+  // exactly one 128 x 128 workgroup per CU (L3 forward of unet_256: 64 x 4 tiles) leaves every CU a single K loop with
+  // nothing to overlap its LDS-DMA round trips; 64-column tiles give each CU two: 52.2 -> 47.9 us (S2 only: measured there)
+  if (d->geom == ADN_GEMM_S2 && bn == 128 && t128 >= 256 && t128 < 512) bn = 64;
+  // 3 x 3 stride-1 convs (DoubleConv nets) with >= 128 output columns: the tall 256 x 64 tile (4 x 1 waves, the same 64 x 64
+  // per wave) has less patch halo per pixel (18 x 18 for 256 pixels instead of 10 x 18 for 128) and half the weight bytes
+  // per K-step: forward convs +5 ... +11 % (up3 conv1 297 -> 274 us, 1 131 TFLOP/s), input gradients 0 ... +8 %; and at the
+  // 16 x 16-image level, where 128-column tiles give one workgroup per CU, 64-column tiles (not tall there) +20 ... +23 %.
+  // RGBDepthNet 256^2 step 13.37 -> 13.11 ms with this rule forced everywhere (ADN_IGEMM_BN=64), so it is the rule now.
+  if (d->geom == ADN_GEMM_S1 && d->ks == 3 && bn == 128 && wide && d->Hs % 8 == 0 && d->Ws % 16 == 0) {
+    const bool tall_ok = d->Hs % 16 == 0 && tn.tall != 0 && msmall / 256 * (d->N / 64) >= 512;
+    if (tall_ok || (t128 >= 256 && t128 < 512)) bn = 64;
+  }
+  return bn;
+}
+
+// Split-K factor of the tile kernel for `tiles` workgroups of `ksteps` K-steps
+int plan_splits(const AdnIgemmDesc* d, int64_t tiles, int ksteps, int64_t mout) {
+  const Tune& tn = tune();
+  int ns = 1;
+  if (tiles < 256) {
+    ns = (int)(512 / tiles);          // stay within one resident wave of workgroups (256 CUs x 2)
+    const int max_by_k = ksteps / 2 > 0 ? ksteps / 2 : 1;
+    if (ns > max_by_k) ns = max_by_k;
+    // more than 16 slabs cost more in slab traffic (ns x M x N x 8 bytes written + read back) than the extra
+    // workgroups return: L5 / L6 forward 23.6 / 20.8 -> 20.3 / 16.1 us, D6 dgrad 25.7 -> 19.4 us at a cap of 16
+    // (bf16 only: in f32 the cap is neutral for speed, and the f32 reference fixtures of the Base+Residual net hold
+    //  gradients through 4 x 4 BatchNorm layers that are sensitive to the summation order at their 5e-3 bound)
+    // ... unless the layer is so small that more slabs still fit in `tinycap` MB (ADN_IGEMM_TINYCAP, default 4: the
+    // 32-row GEMMs of the innermost level run 64 splits = 2 K-steps per workgroup, 17.8 -> 15.4 us incl. the reduce)
+    const bool bf16 = d->dtype == ADN_BF16;
+    int cap = bf16 ? 16 : 64;
+    if (bf16 && tn.tinycap > 0) {
+      const int64_t by_bytes = ((int64_t)tn.tinycap << 20) / (mout * d->N * 4);
+      if (by_bytes > cap) cap = by_bytes > 64 ? 64 : (int)by_bytes;
+    }
+    if (ns > cap) ns = cap;
+    if (ns < 1) ns = 1;
+  }
+  if (tn.ns >= 1 && ns > tn.ns) ns = tn.ns;                  // tuning knob: cap on the split count
+  return ns;
+}
+
+// One unsplit launch of bm x bn tiles that tile the images exactly (Patch, Ring)
+void plan_unsplit(Plan* pl, Kind kind, int bm, int bn, int64_t msmall, int N) {
+  pl->kind = kind;
+  pl->bm = bm;
+  pl->bn = bn;
+  pl->tiles_m = (int)(msmall / bm);
+  pl->tiles_n = N / bn;
+  pl->nsplit = 1;
+  pl->partial_rows = (int64_t)pl->tiles_m * pl->phases;
+  pl->slab_bytes = 0;
+}
+
+void make_plan(const AdnIgemmDesc* d, Plan* pl) {
+  // ---- shared quantities ----
+  const Tune& tn = tune();
+  const bool bf16 = d->dtype == ADN_BF16;
+  const int esz = bf16 ? 2 : 4;
   const int bk = 128 / esz;
   const int Cin = d->C0 + d->C1;
   const int64_t msmall = (int64_t)d->B * d->Hs * d->Ws;
@@ -989,145 +1021,89 @@ bool make_plan(const AdnIgemmDesc* d, Plan* pl) {
   // S1 operands (adn_pack_rows / adn_pack_transpose_taps) pad their rows to the K-step; the k4 packs do not
   pl->wstride = d->geom == ADN_GEMM_S1 ? (int)(adn_cdiv((int64_t)taps * Cin, bk) * bk) : taps * Cin;
   const int epc = 16 / esz;
-  // wide: every K-step lies inside one tap of one source; narrow: single source, several taps per K-step
   pl->wide = (d->C0 % bk == 0) && (d->C1 % bk == 0);
   // (S1 weights are packed with rows zero-padded to the K-step, so taps*Cin need not divide; S2/T2 packs are not)
   const bool narrow_ok = (d->C1 == 0) && (d->C0 % epc == 0) && (d->geom == ADN_GEMM_S1 || (taps * Cin) % bk == 0);
   const bool aligned = (pl->wide || narrow_ok) && (d->N % 64 == 0) && (d->seg[0].channels % 64 == 0) &&
                        (d->seg[1].channels % 64 == 0);
-  pl->mfma = aligned;
-  pl->patch = pl->tall = pl->pair = pl->ring = false;
-  pl->onepx = false;
+  pl->tall = pl->pair = pl->onepx = false;
+  pl->rb = reduce_rows(pl->mout, d->N);
   if (!aligned) {
-    pl->bn = 0;
+    pl->kind = Kind::Direct;
+    pl->bm = pl->bn = 0;
     pl->nsplit = 1;
     pl->tiles_m = pl->tiles_n = 0;
-    pl->kpt = pl->ksteps = 0;
-    pl->rb = reduce_rows(pl->mout, d->N);
+    pl->ksteps = 0;
     pl->partial_rows = adn_cdiv(pl->mout, pl->rb);
     pl->slab_bytes = pl->mout * d->N * 4;
-    return true;
+    return;
   }
-  pl->bn = (d->N % 128 == 0) ? 128 : 64;     // segments are multiples of 64: an 8-channel group never straddles
+  // the tile kernel's plan: the unsplit kernels only take layers that it would not split
   // 256-row tiles (8 waves, 3-stage ring) when they still give every CU a workgroup; else 128-row tiles
   // (only worth it for long K loops: with K <= 1024 two 128-row workgroups per CU overlap each other's
   //  prologue/epilogue better: measured 685 vs 621 TFLOP/s on L1 forward)
-  const bool fills256 = adn_cdiv(msmall, 256) * (d->N / pl->bn) * pl->phases >= 256;
-  pl->bm = (fills256 && (pl->bn == 64 || taps * Cin / bk >= 32)) ? 256 : 128;
-  const Tune& tn = tune();
-  if (tn.bm) pl->bm = tn.bm == 256 ? 256 : 128;
-  if (tn.bn) pl->bn = (tn.bn == 128 && d->N % 128 == 0) ? 128 : 64;
-  // Transposed-conv geometry (forward of the up path, input gradients of the down path): 64-column tiles throughout --
-  // the tall 256 x 64 patch form on the 16 x 16 ... 64 x 64 image levels (less patch halo per pixel, half the weight bytes
-  // per K-step), twice the workgroups on the split-K levels.  Headline step 2.909 -> 2.860 ms and 2.932 -> 2.894 ms on two
-  // boxes (ADN_IGEMM_BN_T2=128 restores 128-column tiles for an A/B; the two-image PAIR form keeps its 128 columns).
-  if (d->geom == ADN_GEMM_T2 && d->dtype == ADN_BF16 && !tn.bn) pl->bn = (tn.bn_t2 == 128 && d->N % 128 == 0) ? 128 : 64;
-  // exactly one 128 x 128 workgroup per CU (L3 forward of unet_256: 64 x 4 tiles) leaves every CU a single K loop with
-  // nothing to overlap its LDS-DMA round trips; 64-column tiles give each CU two: 52.2 -> 47.9 us (S2 only: measured there)
-  if (d->geom == ADN_GEMM_S2 && d->dtype == ADN_BF16 && pl->bn == 128 && !tn.bn) {
-    const int64_t t128 = adn_cdiv(msmall, 128) * (d->N / 128);
-    if (t128 >= 256 && t128 < 512) pl->bn = 64;
-  }
-  // 3 x 3 stride-1 convs (DoubleConv nets) with >= 128 output columns: the tall 256 x 64 tile (4 x 1 waves, the same 64 x 64
-  // per wave) has less patch halo per pixel (18 x 18 for 256 pixels instead of 10 x 18 for 128) and half the weight bytes
-  // per K-step: forward convs +5 ... +11 % (up3 conv1 297 -> 274 us, 1 131 TFLOP/s), input gradients 0 ... +8 %; and at the
-  // 16 x 16-image level, where 128-column tiles give one workgroup per CU, 64-column tiles (not tall there) +20 ... +23 %.
-  // RGBDepthNet 256^2 step 13.37 -> 13.11 ms with this rule forced everywhere (ADN_IGEMM_BN=64), so it is the rule now.
-  if (d->geom == ADN_GEMM_S1 && d->ks == 3 && d->dtype == ADN_BF16 && pl->bn == 128 && !tn.bn && pl->wide &&
-      d->Hs % 8 == 0 && d->Ws % 16 == 0) {
-    const int64_t t128 = adn_cdiv(msmall, 128) * (d->N / 128);
-    const bool tall_ok = d->Hs % 16 == 0 && tn.tall != 0 && msmall / 256 * (d->N / 64) >= 512;
-    if (tall_ok || (t128 >= 256 && t128 < 512)) pl->bn = 64;
-  }
-  pl->tiles_m = (int)adn_cdiv(msmall, pl->bm);
-  pl->tiles_n = d->N / pl->bn;
-  pl->kpt = 0;
+  const int bn0 = (d->N % 128 == 0) ? 128 : 64;
+  const bool fills256 = adn_cdiv(msmall, 256) * (d->N / bn0) * pl->phases >= 256;
+  int bm = (fills256 && (bn0 == 64 || taps * Cin / bk >= 32)) ? 256 : 128;
+  if (tn.bm) bm = tn.bm == 256 ? 256 : 128;
+  const int bn = plan_columns(d, pl->wide, msmall);
   pl->ksteps = pl->wstride / bk;
   // innermost U-Net level (1 x 1 small-grid images): 12 of 16 (S2) / 3 of 4 (T2) taps are padding for EVERY row
-  pl->onepx = d->dtype == ADN_BF16 && pl->wide && d->Hs == 1 && d->Ws == 1 && d->geom != ADN_GEMM_S1 && tn.onepx != 0;
+  pl->onepx = bf16 && pl->wide && d->Hs == 1 && d->Ws == 1 && d->geom != ADN_GEMM_S1 && tn.onepx != 0;
   if (pl->onepx) pl->ksteps = (d->geom == ADN_GEMM_S2 ? 4 : 1) * (Cin / bk);
-  const int64_t tiles = (int64_t)pl->tiles_m * pl->tiles_n * pl->phases;
-  int ns = 1;
-  if (tiles < 256) {
-    ns = (int)(512 / tiles);          // stay within one resident wave of workgroups (256 CUs x 2)
-    const int max_by_k = pl->ksteps / 2 > 0 ? pl->ksteps / 2 : 1;
-    if (ns > max_by_k) ns = max_by_k;
-    // more than 16 slabs cost more in slab traffic (ns x M x N x 8 bytes written + read back) than the extra
-    // workgroups return: L5 / L6 forward 23.6 / 20.8 -> 20.3 / 16.1 us, D6 dgrad 25.7 -> 19.4 us at a cap of 16
-    // (bf16 only: in f32 the cap is neutral for speed, and the f32 reference fixtures of the Base+Residual net hold
-    //  gradients through 4 x 4 BatchNorm layers that are sensitive to the summation order at their 5e-3 bound)
-    // ... unless the layer is so small that more slabs still fit in `tinycap` MB (ADN_IGEMM_TINYCAP, default 4: the
-    // 32-row GEMMs of the innermost level run 64 splits = 2 K-steps per workgroup, 17.8 -> 15.4 us incl. the reduce)
-    int cap = esz == 2 ? 16 : 64;
-    if (esz == 2 && tn.tinycap > 0) {
-      const int64_t by_bytes = ((int64_t)tn.tinycap << 20) / (pl->mout * d->N * 4);
-      if (by_bytes > cap) cap = by_bytes > 64 ? 64 : (int)by_bytes;
-    }
-    if (ns > cap) ns = cap;
-    if (ns < 1) ns = 1;
-  }
-  if (tn.ns >= 1 && ns > tn.ns) ns = tn.ns;                  // tuning knob: cap on the split count
-  pl->nsplit = ns;
-  // patch-staged variant: bf16, every chunk of 32 channels inside one source, images tileable by 8 x 16 output pixels,
-  // enough tiles that no split-K is wanted (ADN_IGEMM_PATCH=0 switches it off)
-  pl->patch = d->dtype == ADN_BF16 && pl->wide && ns == 1 && (d->geom != ADN_GEMM_S1 || d->ks == 3) && d->Hs % 8 == 0 &&
-              d->Ws % 16 == 0 && tn.patch != 0;
+  const int64_t tile_tiles = adn_cdiv(msmall, bm) * (d->N / bn) * pl->phases;
+  const int ns = plan_splits(d, tile_tiles, pl->ksteps, pl->mout);
+  const bool k4 = d->geom == ADN_GEMM_S2 || d->geom == ADN_GEMM_T2;
+
+  // ---- choose the kind: pair, else ring, else patch, else tile ----
   // two 8 x 8 images per tile: replaces the split-K launch + reduce of that level by one unsplit patch launch
   // (T2 only: the S2 form -- D4 dgrad, 128 workgroups x 128 K-steps -- measured 99 us against 40 us for split-K + reduce)
-  pl->pair = d->dtype == ADN_BF16 && pl->wide && d->geom == ADN_GEMM_T2 && d->Hs == 8 && d->Ws == 8 && d->B % 2 == 0 &&
-             d->N % 128 == 0 && tn.pair != 0 && tn.patch != 0 &&
-             msmall / 128 * (d->N / 128) * pl->phases >= 128;      // (64 workgroups with a 128-step K loop lose to split-K: L4 forward)
-  if (pl->pair) {
-    pl->patch = true;
-    pl->bn = 128;
-    pl->tiles_n = d->N / 128;
-    ns = 1;
-    pl->nsplit = 1;
-  }
-  pl->tall = !pl->pair && pl->patch && pl->bn == 64 && d->geom != ADN_GEMM_S2 && d->Hs % 16 == 0 && tn.tall != 0 &&
-             msmall / 256 * pl->tiles_n * pl->phases >= 512;
-  if (pl->patch) {
-    pl->bm = pl->tall ? 256 : 128;
-    pl->tiles_m = (int)(msmall / pl->bm);
-  }
+  const bool pair = bf16 && pl->wide && d->geom == ADN_GEMM_T2 && d->Hs == 8 && d->Ws == 8 && d->B % 2 == 0 &&
+                    d->N % 128 == 0 && tn.pair != 0 && tn.patch != 0 &&
+                    msmall / 128 * (d->N / 128) * pl->phases >= 128;      // (64 workgroups with a 128-step K loop lose to split-K: L4 forward)
   // ring-fed persistent kernel: bf16, wide, unsplit, 16 x 16-pixel tiles, Z_STATS / BWD epilogues, a multiple of 8 K-steps
   // per tile (S2: always; T2: Cin % 128 == 0), every 32-channel chunk inside one source.  (The plan -- and with it the number
   // of partial rows -- depends on the epilogue: adn_igemm_num_partials must be asked with the epilogue of the launch.)
-  pl->ring = false;
-  if (d->dtype == ADN_BF16 && pl->wide && ns == 1 && !pl->pair && (d->geom == ADN_GEMM_S2 || d->geom == ADN_GEMM_T2) &&
-      d->Hs % 16 == 0 && d->Ws % 16 == 0 && (d->N % 128 == 0 || (d->N == 64 && tn.ring64n != 0)) &&
-      (d->geom == ADN_GEMM_S2 || Cin % 128 == 0) && tn.ring != 0 && pl->mout * d->N < (1ll << 31) &&
-      (d->epi == ADN_EPI_Z_STATS || d->epi == ADN_EPI_BWD) && (tn.ring_epi == 0 || tn.ring_epi == d->epi) &&
-      (tn.ring_geom < 0 || tn.ring_geom == d->geom) && (tn.ring_hs == 0 || tn.ring_hs == d->Hs)) {
+  const bool ring = bf16 && pl->wide && ns == 1 && !pair && k4 && d->Hs % 16 == 0 && d->Ws % 16 == 0 &&
+                    (d->N % 128 == 0 || (d->N == 64 && tn.ring64n != 0)) && (d->geom == ADN_GEMM_S2 || Cin % 128 == 0) &&
+                    tn.ring != 0 && pl->mout * d->N < (1ll << 31) && (d->epi == ADN_EPI_Z_STATS || d->epi == ADN_EPI_BWD) &&
+                    (tn.ring_epi == 0 || tn.ring_epi == d->epi) && (tn.ring_geom < 0 || tn.ring_geom == d->geom) &&
+                    (tn.ring_hs == 0 || tn.ring_hs == d->Hs);
+  // patch-staged variant: bf16, every chunk of 32 channels inside one source, images tileable by 8 x 16 output pixels,
+  // enough tiles that no split-K is wanted (ADN_IGEMM_PATCH=0 switches it off)
+  const bool patch = bf16 && pl->wide && ns == 1 && (d->geom != ADN_GEMM_S1 || d->ks == 3) && d->Hs % 8 == 0 &&
+                     d->Ws % 16 == 0 && tn.patch != 0;
+
+  // ---- fill the plan of the kind ----
+  if (pair) {
+    plan_unsplit(pl, Kind::Patch, 128, 128, msmall, d->N);
+    pl->pair = true;
+  } else if (ring) {
     const int64_t t128 = msmall / 256 * (d->N / 128) * pl->phases;
     const int rbn = (d->N == 64 || tn.ring == 64 || (tn.ring != 128 && t128 < 192)) ? 64 : 128;    // too few 128-column tiles to fill the chip: 64
-    pl->ring = true;
-    pl->patch = pl->tall = false;
-    pl->bm = 256;
-    pl->bn = rbn;
-    pl->tiles_m = (int)(msmall / 256);
-    pl->tiles_n = d->N / rbn;
-  }
-  pl->rb = reduce_rows(pl->mout, d->N);
-  if (ns > 1) {
-    pl->partial_rows = adn_cdiv(pl->mout, pl->rb);
-    pl->slab_bytes = (int64_t)ns * pl->mout * d->N * 4;
+    plan_unsplit(pl, Kind::Ring, 256, rbn, msmall, d->N);
+  } else if (patch) {
+    pl->tall = bn == 64 && d->geom != ADN_GEMM_S2 && d->Hs % 16 == 0 && tn.tall != 0 &&
+               msmall / 256 * (d->N / bn) * pl->phases >= 512;
+    plan_unsplit(pl, Kind::Patch, pl->tall ? 256 : 128, bn, msmall, d->N);
   } else {
-    pl->partial_rows = (int64_t)pl->tiles_m * pl->phases;
-    pl->slab_bytes = 0;
+    pl->kind = Kind::Tile;
+    pl->bm = bm;
+    pl->bn = bn;
+    pl->tiles_m = (int)adn_cdiv(msmall, bm);
+    pl->tiles_n = d->N / bn;
+    pl->nsplit = ns;
+    pl->partial_rows = ns > 1 ? adn_cdiv(pl->mout, pl->rb) : (int64_t)pl->tiles_m * pl->phases;
+    pl->slab_bytes = ns > 1 ? (int64_t)ns * pl->mout * d->N * 4 : 0;
   }
-  return true;
 }
 
 template <typename T, int BM_, int BN, int NWN, int GEOM, bool WIDE>
-int launch_mfma(const KParams& kp, const Plan& pl, hipStream_t st) {
-  const int stage = ((BM_ == 256 && NWN == 2) ? 3 : 2) * (BM_ + BN) * 128;
-  const int epil = BM_ * (BN + 4) * 4;
-  const int lds = stage > epil ? stage : epil;
+void launch_mfma(const KParams& kp, const Plan& pl, hipStream_t st) {
+  constexpr int lds = TileCfg<BM_, BN, NWN>::lds_bytes;
   dim3 grid(pl.tiles_m * pl.tiles_n * pl.phases, 1, pl.nsplit);
   ADN_SET_LDS_ONCE(lds, &igemm_mfma_kernel<T, BM_, BN, NWN, GEOM, WIDE>);
   hipLaunchKernelGGL((igemm_mfma_kernel<T, BM_, BN, NWN, GEOM, WIDE>), grid, dim3(BM_ * NWN), lds, st, kp);
-  return 0;
 }
 
 template <typename T, int GEOM, bool WIDE>
@@ -1148,13 +1124,7 @@ void dispatch_mfma(const KParams& kp, const Plan& pl, hipStream_t st) {
 
 template <int BN, int GEOM, bool TALL = false, bool PRE = true, bool PAIR = false>
 void launch_patch1(const KParams& kp, const Plan& pl, hipStream_t st) {
-  constexpr bool S2 = GEOM == ADN_GEMM_S2, S1 = GEOM == ADN_GEMM_S1;
-  constexpr int TH = TALL ? 16 : 8;
-  constexpr int MWc = PAIR ? 18 : 17;
-  constexpr int ppieces = ((S2 ? 2 * (TH + 1) * MWc : (S1 ? (TH + 2) * 18 : (TH + 1) * MWc)) + 15) / 16;
-  constexpr int stage = 2 * ppieces * 1024 + 2 * (S1 ? 3 : 2) * BN * 64;
-  constexpr int epil = TH * 16 * (BN + 4) * 4;
-  constexpr int lds = stage > epil ? stage : epil;
+  constexpr int lds = PatchCfg<BN, GEOM, TALL, PAIR>::lds_bytes;
   ADN_SET_LDS_ONCE(lds, &igemm_patch_kernel<BN, GEOM, TALL, PRE, PAIR>);
   dim3 grid(pl.tiles_m * pl.tiles_n * pl.phases, 1, 1);
   hipLaunchKernelGGL((igemm_patch_kernel<BN, GEOM, TALL, PRE, PAIR>), grid, dim3(256), lds, st, kp);
@@ -1193,8 +1163,7 @@ inline int device_cus() {
 
 template <int GEOM, int BN, int SCHED>
 void launch_ring1(const KParams& kp, const Plan& pl, hipStream_t st) {
-  constexpr bool S2 = GEOM == ADN_GEMM_S2;
-  constexpr int lds = (S2 ? 2 * 40 : 4 * 20) * 1024 + 4 * 2 * BN * 64 + 8 * BN * 4;
+  constexpr int lds = RingCfg<GEOM, BN>::lds_bytes;
   ADN_SET_LDS_ONCE(lds, &igemm_ring_kernel<GEOM, BN, SCHED>);
   const int ntiles = pl.tiles_m * pl.tiles_n * pl.phases;
   const int cus = device_cus();
@@ -1225,7 +1194,6 @@ int run(const AdnIgemmDesc* d, const Plan& pl, hipStream_t st) {
   kp.in0 = d->in0;
   kp.in1 = d->in1;
   kp.w = d->w;
-  kp.B = d->B;
   kp.Hs = d->Hs;
   kp.Ws = d->Ws;
   kp.C0 = d->C0;
@@ -1234,7 +1202,6 @@ int run(const AdnIgemmDesc* d, const Plan& pl, hipStream_t st) {
   kp.ks = d->geom == ADN_GEMM_S1 ? d->ks : 0;
   kp.wstride = pl.wstride;
   kp.Msmall = d->B * d->Hs * d->Ws;
-  kp.kpt = pl.kpt;
   kp.ksteps = pl.ksteps;
   kp.onepx = pl.onepx ? 1 : 0;
   kp.nsplit = pl.nsplit;
@@ -1253,39 +1220,44 @@ int run(const AdnIgemmDesc* d, const Plan& pl, hipStream_t st) {
   kp.rec_a = tune().noa ? 0u : 0x7ffffff0u;
   kp.rec_b = tune().nob ? 0u : 0x7ffffff0u;
   kp.skip = tune().skip;
-  if (pl.mfma && pl.ring) {
-    if constexpr (sizeof(T) == 2) launch_ring(kp, pl, d->geom, st);
-    ADN_CHECK_LAUNCH();
-  } else if (pl.mfma && pl.patch) {
-    if constexpr (sizeof(T) == 2) launch_patch(kp, pl, d->geom, st);
-    ADN_CHECK_LAUNCH();
-  } else if (pl.mfma) {
-    if (d->geom == ADN_GEMM_S2) dispatch_mfma<T, ADN_GEMM_S2>(kp, pl, st);
-    else if (d->geom == ADN_GEMM_T2) dispatch_mfma<T, ADN_GEMM_T2>(kp, pl, st);
-    else dispatch_mfma<T, ADN_GEMM_S1>(kp, pl, st);
-    ADN_CHECK_LAUNCH();
-    if (pl.nsplit > 1) {
-      hipLaunchKernelGGL((igemm_reduce_kernel<T>),
-                         dim3((unsigned)adn_cdiv(pl.mout, pl.rb), (unsigned)adn_cdiv(d->N, 256)), dim3(256), 0, st, kp,
-                         pl.mout, pl.rb);
+  auto reduce = [&]() {
+    hipLaunchKernelGGL((igemm_reduce_kernel<T>), dim3((unsigned)adn_cdiv(pl.mout, pl.rb), (unsigned)adn_cdiv(d->N, 256)),
+                       dim3(256), 0, st, kp, pl.mout, pl.rb);
+  };
+  switch (pl.kind) {
+    case Kind::Ring:
+      if constexpr (sizeof(T) == 2) launch_ring(kp, pl, d->geom, st);
       ADN_CHECK_LAUNCH();
+      break;
+    case Kind::Patch:
+      if constexpr (sizeof(T) == 2) launch_patch(kp, pl, d->geom, st);
+      ADN_CHECK_LAUNCH();
+      break;
+    case Kind::Tile:
+      if (d->geom == ADN_GEMM_S2) dispatch_mfma<T, ADN_GEMM_S2>(kp, pl, st);
+      else if (d->geom == ADN_GEMM_T2) dispatch_mfma<T, ADN_GEMM_T2>(kp, pl, st);
+      else dispatch_mfma<T, ADN_GEMM_S1>(kp, pl, st);
+      ADN_CHECK_LAUNCH();
+      if (pl.nsplit > 1) {
+        reduce();
+        ADN_CHECK_LAUNCH();
+      }
+      break;
+    case Kind::Direct: {
+      const int64_t total = pl.mout * d->N;
+      int64_t blocks = adn_cdiv(total, 256);
+      if (blocks > 65536) blocks = 65536;
+      if (d->geom == ADN_GEMM_S2)
+        hipLaunchKernelGGL((igemm_direct_kernel<T, ADN_GEMM_S2>), dim3((unsigned)blocks), dim3(256), 0, st, kp);
+      else if (d->geom == ADN_GEMM_T2)
+        hipLaunchKernelGGL((igemm_direct_kernel<T, ADN_GEMM_T2>), dim3((unsigned)blocks), dim3(256), 0, st, kp);
+      else
+        hipLaunchKernelGGL((igemm_direct_kernel<T, ADN_GEMM_S1>), dim3((unsigned)blocks), dim3(256), 0, st, kp);
+      ADN_CHECK_LAUNCH();
+      reduce();
+      ADN_CHECK_LAUNCH();
+      break;
     }
-  } else {
-    const int64_t total = pl.mout * d->N;
-    int64_t blocks = adn_cdiv(total, 256);
-    if (blocks > 65536) blocks = 65536;
-    if (d->geom == ADN_GEMM_S2)
-      hipLaunchKernelGGL((igemm_direct_kernel<T, ADN_GEMM_S2>), dim3((unsigned)blocks), dim3(256), 0, st, kp);
-    else if (d->geom == ADN_GEMM_T2)
-      hipLaunchKernelGGL((igemm_direct_kernel<T, ADN_GEMM_T2>), dim3((unsigned)blocks), dim3(256), 0, st, kp);
-    else
-      hipLaunchKernelGGL((igemm_direct_kernel<T, ADN_GEMM_S1>), dim3((unsigned)blocks), dim3(256), 0, st, kp);
-    ADN_CHECK_LAUNCH();
-    kp.nsplit = 1;
-    hipLaunchKernelGGL((igemm_reduce_kernel<T>),
-                       dim3((unsigned)adn_cdiv(pl.mout, pl.rb), (unsigned)adn_cdiv(d->N, 256)), dim3(256), 0, st, kp,
-                       pl.mout, pl.rb);
-    ADN_CHECK_LAUNCH();
   }
   return ADN_OK;
 }
@@ -1337,6 +1309,19 @@ extern "C" int64_t adn_igemm_workspace_bytes(const AdnIgemmDesc* d) {
   Plan pl;
   make_plan(d, &pl);
   return pl.slab_bytes;
+}
+
+extern "C" int adn_igemm_describe(const AdnIgemmDesc* d, char* buf, int len) {
+  int rc = validate(d);
+  if (rc != ADN_OK) return rc;
+  ADN_CHECK_ARG(buf != nullptr && len > 0, "adn_igemm_describe: no buffer");
+  Plan pl;
+  make_plan(d, &pl);
+  const char* kind = pl.kind == Kind::Direct ? "direct" : pl.kind == Kind::Ring ? "ring" : pl.kind == Kind::Tile ? "tile"
+                     : pl.pair ? "patch-pair" : pl.tall ? "patch-tall" : "patch";
+  snprintf(buf, (size_t)len, "%s bm=%d bn=%d nsplit=%d tiles=%dx%dx%d ksteps=%d partials=%lld ws=%lld", kind, pl.bm, pl.bn, pl.nsplit,
+           pl.tiles_m, pl.tiles_n, pl.phases, pl.ksteps, (long long)pl.partial_rows, (long long)pl.slab_bytes);
+  return ADN_OK;
 }
 
 extern "C" int adn_igemm(const AdnIgemmDesc* d, void* stream) {

@@ -115,6 +115,21 @@ struct RingTile {
   int tile_n, phase, tb, oy0, ox0, tile_m;
 };
 
+// LDS layout: [NPBUF patch buffers][RING weight slots][column-sum scratch]; the one source for the kernel and its launcher
+template <int GEOM, int BN>
+struct RingCfg {
+  static constexpr bool S2 = GEOM == ADN_GEMM_S2;
+  static constexpr int PPIECES = S2 ? 40 : 20;      // 1-KiB LDS-DMA pieces per patch segment (S2: 37 used, padded to 8 waves)
+  static constexpr int PBUF = PPIECES * 1024;
+  static constexpr int NPBUF = S2 ? 2 : 4;
+  static constexpr int WBUF = 2 * BN * 64;          // one ring slot: [2 taps][BN rows][64 B]
+  static constexpr int RING = 4;
+  static constexpr int W_OFF = NPBUF * PBUF, R_OFF = W_OFF + RING * WBUF;
+  static constexpr int RED_BYTES = 8 * 2 * (BN / 2) * 4;       // [8 waves][2][BN/2] f32
+  static constexpr int lds_bytes = R_OFF + RED_BYTES;
+  static_assert(lds_bytes <= LDS_MAX, "ring kernel: LDS budget");
+};
+
 template <int GEOM, int BN, int SCHED>
 __global__ __launch_bounds__(512, 2) void igemm_ring_kernel(KParams p, int ntiles, int nwgs, unsigned mg_tn, unsigned mg_tpi,
                                                              unsigned mg_tpr) {
@@ -123,17 +138,14 @@ __global__ __launch_bounds__(512, 2) void igemm_ring_kernel(KParams p, int ntile
   constexpr int MW = 17, PLANE = 17 * 17;
   constexpr int SEG_PIX = S2 ? 2 * PLANE : PLANE;
   constexpr int SEG_STEPS = S2 ? 4 : 2;
-  constexpr int PPIECES = S2 ? 40 : 20;             // 1-KiB LDS-DMA pieces per patch segment (S2: 37 used, padded to 8 waves)
+  using Cfg = RingCfg<GEOM, BN>;
+  constexpr int PBUF = Cfg::PBUF, NPBUF = Cfg::NPBUF, WBUF = Cfg::WBUF, RING = Cfg::RING, W_OFF = Cfg::W_OFF, R_OFF = Cfg::R_OFF;
   constexpr int PKW = S2 ? 5 : 3;                   // pieces per wave (T2: waves 4..7 repeat pieces 16..19 of waves 0..3)
-  constexpr int PBUF = PPIECES * 1024;
-  constexpr int NPBUF = S2 ? 2 : 4;
   constexpr int PAHEAD = S2 ? 1 : 2;                // segments the patch requests run ahead of the compute
   constexpr int NT = BN / 32;                       // 16-channel MFMA tiles per wave (two waves along the channels)
   constexpr int NH = NT / 2;                        // 8-channel (16-byte) output groups per lane
   constexpr int WPW = BN / 64;                      // weight pieces per wave and K-step
-  constexpr int WBUF = 2 * BN * 64;                 // one ring slot: [2 taps][BN rows][64 B]
-  constexpr int RING = 4, WAHEAD = 3;
-  constexpr int W_OFF = NPBUF * PBUF, R_OFF = W_OFF + RING * WBUF;
+  constexpr int WAHEAD = RING - 1;
   constexpr int NPH = S2 ? 1 : 4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 

@@ -113,6 +113,10 @@ int adn_debug_stream_rmw(const void* src, void* dst, int64_t bytes, int32_t work
 /* Number of stats partial rows P the implicit GEMM will write for this descriptor. */
 int64_t adn_igemm_num_partials(const AdnIgemmDesc* d);
 int64_t adn_igemm_workspace_bytes(const AdnIgemmDesc* d);
+/* Host only: the plan of this descriptor (kernel form, tile, split count, grid, K-steps, the two answers above) as one
+ * line of text in buf, e.g. "ring bm=256 bn=128 nsplit=1 tiles=128x2x4 ksteps=16 partials=512 ws=0".  The form is one of
+ * direct | tile | patch | patch-tall | patch-pair | ring; like the partial rows it depends on the epilogue. */
+int adn_igemm_describe(const AdnIgemmDesc* d, char* buf, int len);
 
 /* Implicit-GEMM convolution family.
  * Replaces: nn.Conv2d(k4,s2,p1) forward  (models/unetbaseline_model.py:187-188)   [S2]

@@ -59,22 +59,25 @@ def ws_for(dtype, geom, B, Hs, Ws, C0, C1, N, segs, epi=0):
 TOL_F32_OUT = {torch.float32: 2e-5, torch.bfloat16: 1e-4}
 TOL_T_OUT = {torch.float32: 2e-5, torch.bfloat16: 6e-3}
 
-# (B, Cin0, Cin1, Cout, Hsmall)   Hsmall = small-grid side
+# (B, Cin0, Cin1, Cout, Hsmall)   Hsmall = small-grid side.  The labels name the kernel form of the bf16 launches of the three
+# forward / input-gradient tests below (RAW epilogue; f32 always runs the tile or the direct kernel); IGEMM_FORMS holds the
+# form of every launch and tests/test_host_logic.py checks it against adn_igemm_describe.
 SHAPES = [
-    (2, 64, 0, 128, 16),     # MFMA, BN=128
-    (2, 64, 64, 64, 8),      # MFMA, BN=64, two gathered sources (virtual concat)
-    (3, 128, 0, 128, 2),     # MFMA, tiny M -> split-K + reduce
-    (8, 64, 0, 128, 64),     # MFMA, >=256 tiles -> fused LDS epilogue (BN=128)
-    (8, 64, 64, 64, 32),     # MFMA, fused epilogue for the 4-phase T2 geometry (BN=64)
-    (16, 64, 0, 128, 64),    # MFMA, 256-row tiles / 8 waves / 3-stage LDS-DMA ring (S2: 256 tiles)
-    (16, 64, 64, 64, 32),    # same for T2 (64 tiles x 4 phases), BN=64
+    (2, 64, 0, 128, 16),     # 1 ... 8 tiles -> split-K + reduce (128 x 128 tiles; T2: 128 x 64)
+    (2, 64, 64, 64, 8),      # split-K, 128 x 64 tiles, two gathered sources (virtual concat)
+    (3, 128, 0, 128, 2),     # tiny M -> split-K + reduce, the last tile mostly beyond M
+    (8, 64, 0, 128, 64),     # S2: patch kernel, 128 x 64 tiles (t128 rule); T2: tall patch; f32: unsplit 128 x 128 tiles, LDS epilogue
+    (8, 64, 64, 64, 32),     # patch kernel, 128 x 64 tiles, two gathered sources; f32: unsplit 128 x 64 tiles, 4-phase T2
+    (16, 64, 0, 128, 64),    # S2: patch kernel, 128 x 128 tiles; f32: 256-row tiles / 8 waves / 3-stage LDS-DMA ring (256 tiles)
+    (16, 64, 64, 64, 32),    # patch kernel, 128 x 64; f32 T2: 256 x 64 tiles (64 tiles x 4 phases)
     (8, 64, 64, 64, 64),     # T2: 128 tiles of 16 x 16 pixels x 4 phases -> the tall 4 x 1-wave patch kernel (BN = 64)
-    (4, 128, 0, 256, 8),     # 8 x 8 small-grid images: two images per patch tile (PAIR form), S2 and T2
-    (6, 64, 64, 128, 8),     # PAIR form with two gathered sources, three image pairs
+    (4, 128, 0, 256, 8),     # 8 x 8 small-grid images below the PAIR threshold (16 < 128 workgroups): split-K, S2 and T2
+    (6, 64, 64, 128, 8),     # the same with two gathered sources, three image pairs: split-K
     (32, 128, 0, 128, 1),    # 1 x 1 small-grid images (innermost level): only the 4 (S2) / 1 (T2 phase) in-range taps are walked
     (8, 64, 64, 128, 1),     # same with two gathered sources
     (2, 6, 0, 10, 4),        # generic direct path
     (1, 3, 5, 1, 5),         # generic, two sources, single output channel, odd size
+    (32, 128, 0, 256, 8),    # T2: two 8 x 8 images per patch tile (PAIR form, 16 x 2 x 4 = 128 workgroups); S2: split-K
 ]
 
 
@@ -254,12 +257,19 @@ def test_wgrad_norm_partials(dtype, shape):
     assert abs(float(state_a[4]) - float(state_b[4])) <= 1e-9 * float(state_a[4])
 
 
+Z_SHAPES = [(2, 64, 0, 128, 16), (3, 128, 0, 128, 2),     # split-K + reduce
+            (2, 6, 0, 10, 4),         # direct
+            (8, 64, 0, 128, 64),      # ring kernel, 64-column tiles (128 < 192 tiles of 128 columns); f32: 128 x 128 tiles, unsplit
+            (16, 64, 0, 128, 64),     # ring kernel, 128-column tiles, one tile per workgroup; f32: 256 x 128 tiles
+            (20, 64, 0, 128, 64),     # ring kernel, 128-column tiles, 320 tiles on <= 256 workgroups
+            (16, 128, 0, 256, 32),    # ring kernel, 64-column tiles (too few 128-column ones)
+            (12, 64, 0, 384, 32),     # ring kernel, 64-column tiles, 6 column tiles per pixel tile, 288 tiles
+            (8, 64, 0, 64, 64),       # ring kernel, N = 64; f32: 128 x 64 tiles, unsplit
+            (16, 64, 0, 64, 64)]      # ring kernel, N = 64; f32: 256 x 64 tiles
+
+
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize('shape', [(2, 64, 0, 128, 16), (3, 128, 0, 128, 2), (2, 6, 0, 10, 4), (8, 64, 0, 128, 64),
-                                   (16, 64, 0, 128, 64),
-                                   (20, 64, 0, 128, 64),     # ring kernel, 128-column tiles, 320 tiles on <= 256 workgroups
-                                   (16, 128, 0, 256, 32),    # ring kernel, 64-column tiles (too few 128-column ones)
-                                   (12, 64, 0, 384, 32)])    # ring kernel, 64-column tiles, 6 column tiles per pixel tile, 288 tiles
+@pytest.mark.parametrize('shape', Z_SHAPES)
 def test_epilogue_z_stats_and_bn(dtype, shape):
     """Z_STATS epilogue + adn_bn_fwd_finalize + adn_bn_act == conv -> BatchNorm2d(train) -> LeakyReLU / ReLU."""
     B, C0, _, N, Hs = shape
@@ -294,11 +304,14 @@ def test_epilogue_z_stats_and_bn(dtype, shape):
     assert rel_err(from_nhwc(relu), F.relu(yref)) <= 3 * TOL_T_OUT[dtype]
 
 
+BWD2_SHAPES = [(2, 128, 0, 64, 8), (2, 10, 0, 6, 4), (8, 128, 0, 64, 64), (16, 128, 0, 64, 64),
+               (16, 128, 0, 128, 64),    # ring kernel: S2 BWD with two 128-channel segments, T2 BWD accumulating
+               (20, 128, 0, 64, 64),     # ring kernel: the two segments inside ONE 128-column tile, 320 tiles
+               (32, 64, 0, 128, 64)]     # ring kernel: D1 dgrad of unet_256 at B = 32 (4 tiles per workgroup, 2 super-steps)
+
+
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize('shape', [(2, 128, 0, 64, 8), (2, 10, 0, 6, 4), (8, 128, 0, 64, 64), (16, 128, 0, 64, 64),
-                                   (16, 128, 0, 128, 64),    # ring kernel: S2 BWD with two 128-channel segments, T2 BWD accumulating
-                                   (20, 128, 0, 64, 64),     # ring kernel: the two segments inside ONE 128-column tile, 320 tiles
-                                   (32, 64, 0, 128, 64)])    # ring kernel: D1 dgrad of unet_256 at B = 32 (4 tiles per workgroup, 2 super-steps)
+@pytest.mark.parametrize('shape', BWD2_SHAPES)
 def test_epilogue_bwd_two_segments(dtype, shape):
     """convT dgrad with ReLU mask, split into a skip segment (no stats) and an up segment (BN-bwd stats),
     then accumulate a second contribution with a LeakyReLU mask."""
@@ -429,9 +442,14 @@ def test_wgrad_batch_equals_single_launches():
         k.wgrad_batch(dtype, B, [bad])
 
 
+MASKZ_CASES = [(0, (16, 128, 128, 64)), (0, (32, 64, 256, 64)), (1, (16, 256, 128, 16)), (1, (8, 128, 64, 32)),
+               (0, (2, 128, 128, 8)),
+               (1, (8, 64, 64, 64)),       # tall patch kernel, T2 (64 gathered channels: not the ring kernel's)
+               (1, (32, 128, 256, 8))]     # PAIR form of the patch kernel (two 8 x 8 images per tile)
+
+
 @pytest.mark.parametrize('accumulate', [False, True])
-@pytest.mark.parametrize('geom,shape', [(0, (16, 128, 128, 64)), (0, (32, 64, 256, 64)), (1, (16, 256, 128, 16)),
-                                        (1, (8, 128, 64, 32)), (0, (2, 128, 128, 8))])
+@pytest.mark.parametrize('geom,shape', MASKZ_CASES)
 def test_epilogue_bwd_mask_from_z(geom, shape, accumulate):
     """BWD epilogue with the forward's scale / shift passed along (bf16): ref = act(z * scale + shift) as the forward's
     apply kernel writes it, so a kernel may take the mask from z and skip ref -- the ring kernel does (first four
@@ -471,10 +489,15 @@ def test_epilogue_bwd_mask_from_z(geom, shape, accumulate):
     assert rel_err(partials[:, 1].sum(0), (g_ref * xhat).sum((0, 2, 3))) <= 2e-3
 
 
-@pytest.mark.parametrize('shape', [(8, 64, 64, 128, 32),      # ring kernel T2, 64-column tiles, two gathered sources
-                                   (16, 128, 128, 128, 32),   # ring kernel T2, 128-column tiles
-                                   (5, 128, 0, 256, 64),      # ring kernel T2, 320 pixel tiles x 4 phases x 2 column tiles
-                                   (2, 64, 64, 128, 16)])     # (split-K path for comparison)
+ZT2_SHAPES = [(8, 64, 64, 128, 32),      # ring kernel T2, 64-column tiles, two gathered sources
+              (16, 128, 128, 128, 32),   # ring kernel T2, 128-column tiles
+              (5, 128, 0, 256, 64),      # ring kernel T2, 320 pixel tiles x 4 phases x 2 column tiles
+              (2, 64, 64, 128, 16),      # (split-K path for comparison)
+              (8, 64, 0, 64, 64),        # tall patch kernel (64 gathered channels: not the ring kernel's)
+              (32, 128, 0, 256, 8)]      # PAIR form of the patch kernel (two 8 x 8 images per tile)
+
+
+@pytest.mark.parametrize('shape', ZT2_SHAPES)
 def test_convT_z_stats_t2(shape):
     """Z_STATS epilogue of the transposed-conv geometry in bf16 (the up path's forward): z and the BatchNorm column sums
     against ConvTranspose2d; the large shapes run the ring-fed persistent kernel (igemm_ring.h)."""
@@ -495,6 +518,143 @@ def test_convT_z_stats_t2(shape):
     assert rel_err(from_nhwc(z), zref) <= TOL_T_OUT[dtype]
     assert rel_err(partials[:, 0].double().sum(0).float(), zref.sum((0, 2, 3))) <= 2e-4
     assert rel_err(partials[:, 1].double().sum(0).float(), (zref * zref).sum((0, 2, 3))) <= 2e-4
+
+
+# Patch kernel with the Z_STATS / BWD epilogues: 16 x 16-tileable images go to the ring kernel, so these run 8 x 16 small-grid
+# images (one patch tile each) at the smallest B that plans unsplit: (geom, B, C0, N)
+PATCH_STATS_CASES = [(0, 64, 64, 512), (1, 16, 64, 256)]
+PATCH_HS, PATCH_WS = 8, 16
+
+
+@pytest.mark.parametrize('epi', [1, 3])
+@pytest.mark.parametrize('geom,B,C0,N', PATCH_STATS_CASES)
+def test_patch_kernel_stats_epilogues(geom, B, C0, N, epi):
+    """The 8 x 16-pixel patch kernel (bf16) with the BatchNorm-forward sums (Z_STATS) and with the backward epilogue (mask,
+    accumulate, BatchNorm-backward sums): outputs at the bf16 bound, column sums as in the tests above."""
+    dtype, Hs, Ws = torch.bfloat16, PATCH_HS, PATCH_WS
+    torch.manual_seed(17)
+    k = K()
+    if geom == 0:
+        x = rounded(torch.randn(B, C0, 2 * Hs, 2 * Ws), dtype)
+        w = rounded(torch.randn(N, C0, 4, 4) * 0.1, dtype)
+        v = F.conv2d(x, w, stride=2, padding=1)
+        w_op, Ho, Wo = pack(w, dtype)[0], Hs, Ws
+    else:
+        x = rounded(torch.randn(B, C0, Hs, Ws), dtype)
+        w = rounded(torch.randn(C0, N, 4, 4) * 0.1, dtype)
+        v = F.conv_transpose2d(x, w, stride=2, padding=1)
+        w_op, Ho, Wo = pack(w, dtype)[1], 2 * Hs, 2 * Ws
+    P, ws = ws_for(dtype, geom, B, Hs, Ws, C0, 0, N, [N], epi=epi)
+    assert ws.numel() == 4 and P == B * (4 if geom else 1)        # unsplit, one partial row per tile and phase
+    partials = torch.zeros(P, 2, N, dtype=torch.float32, device=DEV)
+    if epi == 1:
+        z = torch.empty(B, Ho, Wo, N, dtype=dtype, device=DEV)
+        k.igemm(dtype, geom, B, Hs, Ws, nhwc(x, dtype), None, w_op, N, 1, [k.Seg(N, out0=z, partials=partials)], ws)
+        assert rel_err(from_nhwc(z), v) <= TOL_T_OUT[dtype]
+        assert rel_err(partials[:, 0].double().sum(0).float(), v.sum((0, 2, 3))) <= 2e-4
+        assert rel_err(partials[:, 1].double().sum(0).float(), (v * v).sum((0, 2, 3))) <= 2e-4
+        return
+    ref_act = rounded(torch.randn(B, N, Ho, Wo), dtype)
+    zfwd = rounded(torch.randn(B, N, Ho, Wo), dtype)
+    old = rounded(torch.randn(B, N, Ho, Wo), dtype)
+    mean, istd = torch.randn(N) * 0.1, torch.rand(N) + 0.5
+    g_ref = v * torch.where(ref_act > 0, 1.0, 0.2) + old
+    xhat = (zfwd - mean.view(1, -1, 1, 1)) * istd.view(1, -1, 1, 1)
+    out = nhwc(old, dtype).clone()
+    seg = k.Seg(N, out0=out, ref=nhwc(ref_act, dtype), z=nhwc(zfwd, dtype), mean=mean.to(DEV), istd=istd.to(DEV),
+                partials=partials, slope=0.2, accumulate=True)
+    k.igemm(dtype, geom, B, Hs, Ws, nhwc(x, dtype), None, w_op, N, 3, [seg], ws)
+    assert rel_err(from_nhwc(out), g_ref) <= 2 * TOL_T_OUT[dtype]
+    assert rel_err(partials[:, 0].sum(0), g_ref.sum((0, 2, 3))) <= 2e-3
+    assert rel_err(partials[:, 1].sum(0), (g_ref * xhat).sum((0, 2, 3))) <= 2e-3
+
+
+# The kernel form every bf16 launch of the igemm tests is meant to reach (`test/geometry/BxHsxWs_C0+C1_N`, names as
+# igemm_launches() below builds them): kernel, tile rows x columns, `split` = split-K + reduce.  f32 launches run the tile
+# or the direct kernel; tests/golden/igemm_plans.json holds their plans.
+IGEMM_FORMS = {
+    'fwd/S2/2x16x16_64+0_128': 'tile 128x128 split', 'fwd/T2/2x16x16_64+0_128': 'tile 128x64 split',
+    'dgrad/T2/2x16x16_128+0_64': 'tile 128x64 split', 'dgrad/S2/2x16x16_128+0_64': 'tile 128x64 split',
+    'fwd/S2/2x8x8_64+64_64': 'tile 128x64 split', 'fwd/T2/2x8x8_64+64_64': 'tile 128x64 split',
+    'dgrad/T2/2x8x8_64+0_128': 'tile 128x64 split', 'dgrad/S2/2x8x8_64+0_128': 'tile 128x128 split',
+    'fwd/S2/3x2x2_128+0_128': 'tile 128x128 split', 'fwd/T2/3x2x2_128+0_128': 'tile 128x64 split',
+    'dgrad/T2/3x2x2_128+0_128': 'tile 128x64 split', 'dgrad/S2/3x2x2_128+0_128': 'tile 128x128 split',
+    'fwd/S2/8x64x64_64+0_128': 'patch 128x64', 'fwd/T2/8x64x64_64+0_128': 'patch-tall 256x64',
+    'dgrad/T2/8x64x64_128+0_64': 'patch-tall 256x64', 'dgrad/S2/8x64x64_128+0_64': 'patch 128x64',
+    'fwd/S2/8x32x32_64+64_64': 'tile 128x64 split', 'fwd/T2/8x32x32_64+64_64': 'patch 128x64',
+    'dgrad/T2/8x32x32_64+0_128': 'patch 128x64', 'dgrad/S2/8x32x32_64+0_128': 'tile 128x128 split',
+    'fwd/S2/16x64x64_64+0_128': 'patch 128x128', 'fwd/T2/16x64x64_64+0_128': 'patch-tall 256x64',
+    'dgrad/T2/16x64x64_128+0_64': 'patch-tall 256x64', 'dgrad/S2/16x64x64_128+0_64': 'patch 128x64',
+    'fwd/S2/16x32x32_64+64_64': 'tile 128x64 split', 'fwd/T2/16x32x32_64+64_64': 'patch 128x64',
+    'dgrad/T2/16x32x32_64+0_128': 'patch-tall 256x64', 'dgrad/S2/16x32x32_64+0_128': 'tile 128x128 split',
+    'fwd/S2/8x64x64_64+64_64': 'patch 128x64', 'fwd/T2/8x64x64_64+64_64': 'patch-tall 256x64',
+    'dgrad/T2/8x64x64_64+0_128': 'patch-tall 256x64', 'dgrad/S2/8x64x64_64+0_128': 'patch 128x64',
+    'fwd/S2/4x8x8_128+0_256': 'tile 128x128 split', 'fwd/T2/4x8x8_128+0_256': 'tile 128x64 split',
+    'dgrad/T2/4x8x8_256+0_128': 'tile 128x64 split', 'dgrad/S2/4x8x8_256+0_128': 'tile 128x128 split',
+    'fwd/S2/6x8x8_64+64_128': 'tile 128x128 split', 'fwd/T2/6x8x8_64+64_128': 'tile 128x64 split',
+    'dgrad/T2/6x8x8_128+0_128': 'tile 128x64 split', 'dgrad/S2/6x8x8_128+0_128': 'tile 128x128 split',
+    'fwd/S2/32x8x8_128+0_256': 'tile 128x128 split', 'fwd/T2/32x8x8_128+0_256': 'patch-pair 128x128',
+    'dgrad/T2/32x8x8_256+0_128': 'tile 128x64 split', 'dgrad/S2/32x8x8_256+0_128': 'tile 128x128 split',
+    'fwd/S2/32x1x1_128+0_128': 'tile 128x128 split', 'fwd/T2/32x1x1_128+0_128': 'tile 128x64',
+    'dgrad/T2/32x1x1_128+0_128': 'tile 128x64', 'dgrad/S2/32x1x1_128+0_128': 'tile 128x128 split',
+    'fwd/S2/8x1x1_64+64_128': 'tile 128x128 split', 'fwd/T2/8x1x1_64+64_128': 'tile 128x64',
+    'dgrad/T2/8x1x1_128+0_128': 'tile 128x64', 'dgrad/S2/8x1x1_128+0_128': 'tile 128x128 split',
+    'fwd/S2/2x4x4_6+0_10': 'direct', 'fwd/T2/2x4x4_6+0_10': 'direct', 'dgrad/T2/2x4x4_10+0_6': 'direct',
+    'dgrad/S2/2x4x4_10+0_6': 'direct', 'fwd/S2/1x5x5_3+5_1': 'direct', 'fwd/T2/1x5x5_3+5_1': 'direct',
+    'dgrad/T2/1x5x5_1+0_8': 'direct', 'dgrad/S2/1x5x5_1+0_8': 'direct',
+    'z_stats/S2/2x16x16_64+0_128': 'tile 128x128 split', 'z_stats/S2/3x2x2_128+0_128': 'tile 128x128 split',
+    'z_stats/S2/2x4x4_6+0_10': 'direct', 'z_stats/S2/8x64x64_64+0_128': 'ring 256x64',
+    'z_stats/S2/16x64x64_64+0_128': 'ring 256x128', 'z_stats/S2/20x64x64_64+0_128': 'ring 256x128',
+    'z_stats/S2/16x32x32_128+0_256': 'ring 256x64', 'z_stats/S2/12x32x32_64+0_384': 'ring 256x64',
+    'z_stats/S2/8x64x64_64+0_64': 'ring 256x64', 'z_stats/S2/16x64x64_64+0_64': 'ring 256x64',
+    'bwd2/S2/2x8x8_128+0_128': 'tile 128x128 split', 'bwd2/T2/2x4x4_128+0_64': 'tile 128x64 split',
+    'bwd2/S2/2x4x4_10+0_12': 'direct', 'bwd2/T2/2x2x2_10+0_6': 'direct', 'bwd2/S2/8x64x64_128+0_128': 'ring 256x64',
+    'bwd2/T2/8x32x32_128+0_64': 'ring 256x64', 'bwd2/S2/16x64x64_128+0_128': 'ring 256x128',
+    'bwd2/T2/16x32x32_128+0_64': 'ring 256x64', 'bwd2/S2/16x64x64_128+0_256': 'ring 256x128',
+    'bwd2/T2/16x32x32_128+0_128': 'ring 256x128', 'bwd2/S2/20x64x64_128+0_128': 'ring 256x128',
+    'bwd2/T2/20x32x32_128+0_64': 'ring 256x64', 'bwd2/S2/32x64x64_64+0_256': 'ring 256x128',
+    'bwd2/T2/32x32x32_64+0_128': 'patch-tall 256x64', 'maskz/S2/16x64x64_128+0_128': 'ring 256x128',
+    'maskz/S2/32x64x64_64+0_256': 'ring 256x128', 'maskz/T2/16x16x16_256+0_128': 'ring 256x64',
+    'maskz/T2/8x32x32_128+0_64': 'ring 256x64', 'maskz/S2/2x8x8_128+0_128': 'tile 128x128 split',
+    'maskz/T2/8x64x64_64+0_64': 'patch-tall 256x64', 'maskz/T2/32x8x8_128+0_256': 'patch-pair 128x128',
+    'z_t2/T2/8x32x32_64+64_128': 'ring 256x64', 'z_t2/T2/16x32x32_128+128_128': 'ring 256x128',
+    'z_t2/T2/5x64x64_128+0_256': 'ring 256x128', 'z_t2/T2/2x16x16_64+64_128': 'tile 128x64 split',
+    'z_t2/T2/8x64x64_64+0_64': 'patch-tall 256x64', 'z_t2/T2/32x8x8_128+0_256': 'patch-pair 128x128',
+    'patch_stats1/S2/64x8x16_64+0_512': 'patch 128x64', 'patch_stats3/S2/64x8x16_64+0_512': 'patch 128x64',
+    'patch_stats1/T2/16x8x16_64+0_256': 'patch 128x64', 'patch_stats3/T2/16x8x16_64+0_256': 'patch 128x64',
+}
+
+
+def igemm_launches():
+    """Every adn_igemm launch of the igemm tests of this module as the planner sees it (rows in the form of
+    tools/igemm_plan_table.py; the name is `test/geometry/shape/dtype`).  Host only."""
+    rows = []
+
+    def add(test, dt, geom, B, Hs, C0, C1, N, epi, segs=None, Ws=None):
+        tag = 'bf16' if dt else 'f32'
+        shape = '%dx%dx%d_%d+%d_%d' % (B, Hs, Hs if Ws is None else Ws, C0, C1, N)
+        rows.append(dict(name='%s/%s/%s/%s' % (test, 'ST'[geom] + '2', shape, tag), dtype=dt, geom=geom, B=B, Hs=Hs,
+                         Ws=Hs if Ws is None else Ws, C0=C0, C1=C1, N=N, epi=epi, segs=segs or [N], ks=0))
+
+    for dt in (0, 1):                       # ADN_F32, ADN_BF16
+        for B, C0, C1, N, Hs in SHAPES:
+            add('fwd', dt, 0, B, Hs, C0, C1, N, 0)
+            add('fwd', dt, 1, B, Hs, C0, C1, N, 0)
+            add('dgrad', dt, 1, B, Hs, N, 0, C0 + C1, 0)
+            add('dgrad', dt, 0, B, Hs, N, 0, C0 + C1, 0)
+        for B, C0, _, N, Hs in Z_SHAPES:
+            add('z_stats', dt, 0, B, Hs, C0, 0, N, 1)
+        for B, Cz, _, Chalf, Hs in BWD2_SHAPES:
+            add('bwd2', dt, 0, B, Hs, Cz, 0, 2 * Chalf, 3, segs=[Chalf, Chalf])
+            add('bwd2', dt, 1, B, Hs // 2, Cz, 0, Chalf, 3)
+    for geom, (B, Cz, N, Hs) in MASKZ_CASES:
+        add('maskz', 1, geom, B, Hs, Cz, 0, N, 3)
+    for B, C0, C1, N, Hs in ZT2_SHAPES:
+        add('z_t2', 1, 1, B, Hs, C0, C1, N, 1)
+    for geom, B, C0, N in PATCH_STATS_CASES:
+        for epi in (1, 3):
+            add('patch_stats%d' % epi, 1, geom, B, PATCH_HS, C0, 0, N, epi, Ws=PATCH_WS)
+    return rows
 
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])

@@ -191,3 +191,97 @@ def test_wgrad_plans_with_patch_kernels_off_match_recorded_table():
     assert json.loads(out) == table['rows_patch_off']
     on = {r['name']: r for r in table['rows']}
     assert any(r['workspace_bytes'] != on[r['name']]['workspace_bytes'] for r in table['rows_patch_off'])
+
+
+def _igemm_plan_tool():
+    import importlib.util
+    path = os.path.join(os.path.dirname(GOLDEN), '..', 'tools', 'igemm_plan_table.py')
+    spec = importlib.util.spec_from_file_location('igemm_plan_table', os.path.abspath(path))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _igemm_form(plan):
+    """'ring bm=256 bn=128 nsplit=1 ...' -> 'ring 256x128' (direct: 'direct'; split-K: '... split')."""
+    import re
+    m = re.match(r'(\S+) bm=(\d+) bn=(\d+) nsplit=(\d+) ', plan)
+    kind, bm, bn, ns = m.group(1), int(m.group(2)), int(m.group(3)), int(m.group(4))
+    return 'direct' if kind == 'direct' else '%s %dx%d%s' % (kind, bm, bn, ' split' if ns > 1 else '')
+
+
+def test_igemm_plans_match_recorded_table():
+    """adn_igemm_describe (host only) answers what tests/golden/igemm_plans.json recorded from the library before the
+    planner was restructured around a kernel kind (tools/igemm_plan_table.py writes the table from any build): kernel form,
+    tile, split count, grid, K-steps, partial rows and workspace bytes of every unet_256 layer, the benchmarked shapes, the
+    shapes of the GPU tests and rows on both sides of every planning rule."""
+    tool = _igemm_plan_tool()
+    table = json.load(open(os.path.join(GOLDEN, 'igemm_plans.json')))
+    assert len(table['rows']) >= 400
+    for r in table['rows']:
+        got = tool.query_row(r)
+        assert got == {k: r[k] for k in got}, r['name']
+        assert r['plan'].endswith('partials=%d ws=%d' % (r['num_partials'], r['workspace_bytes'])), r['name']
+    # the recorded table must itself hold what it is meant to pin: every form, and both sides of the rule boundaries
+    plan = {r['name']: r['plan'] for r in table['rows']}
+    assert {p.split()[0] for p in plan.values()} == {'direct', 'tile', 'patch', 'patch-tall', 'patch-pair', 'ring'}
+    assert all(p.split()[0] in ('direct', 'tile') for n, p in plan.items() if n.endswith('f32'))
+    assert 'bn=128' in plan['rule_s2_t128_b127_n128_bf16'] and 'bn=64' in plan['rule_s2_t128_b128_n128_bf16']
+    assert 'bn=64' in plan['rule_s2_t128_b255_n128_bf16'] and 'bn=128' in plan['rule_s2_t128_b128_n256_bf16']
+    assert plan['rule_ring_s2_b191_bf16'].startswith('ring bm=256 bn=64') and plan['rule_ring_s2_b192_bf16'].startswith('ring bm=256 bn=128')
+    assert plan['rule_ring_t2_b47_bf16'].startswith('ring bm=256 bn=64') and plan['rule_ring_t2_b48_bf16'].startswith('ring bm=256 bn=128')
+    assert plan['rule_pair_b30_n256_bf16'].startswith('tile') and plan['rule_pair_b32_n256_bf16'].startswith('patch-pair')
+    assert plan['rule_tall_t2_b127_bf16'].startswith('patch ') and plan['rule_tall_t2_b128_bf16'].startswith('patch-tall')
+    assert [plan['rule_tinycap_b%d_n%d_bf16' % bn].split()[3] for bn in ((8, 128), (16, 512), (32, 512))] == ['nsplit=64', 'nsplit=32', 'nsplit=16']
+    assert plan['unet256_D4_fwd_bf16'].startswith('patch-pair') and plan['unet256_D1_dgrad_bf16'].startswith('ring')
+
+
+@pytest.mark.parametrize('section', ['rows_ring_off', 'rows_patch_off', 'rows_bn_t2_128'])
+def test_igemm_plans_with_knobs_match_recorded_table(section):
+    """ADN_IGEMM_RING=0 / ADN_IGEMM_PATCH=0 / ADN_IGEMM_BN_T2=128 (read once per process, hence the child)."""
+    import subprocess
+    import sys
+    tool = _igemm_plan_tool()
+    table = json.load(open(os.path.join(GOLDEN, 'igemm_plans.json')))
+    out = subprocess.run([sys.executable, tool.__file__, '--query', section], env=dict(os.environ, **tool.KNOBS[section]),
+                         capture_output=True, text=True, check=True).stdout
+    assert len(table[section]) >= 30
+    assert json.loads(out) == table[section]
+    on = {r['name']: r['plan'] for r in table['rows']}
+    assert any(r['plan'] != on[r['name']] for r in table[section])
+    kinds = {r['plan'].split()[0] for r in table[section]}
+    if section == 'rows_ring_off':
+        assert 'ring' not in kinds
+    if section == 'rows_patch_off':
+        assert not any(k.startswith('patch') for k in kinds)
+
+
+def test_igemm_gpu_test_shapes_reach_the_forms_they_name():
+    """Every bf16 launch of the igemm tests of test_gpu_kernels.py runs the kernel form IGEMM_FORMS names for it, and the
+    forms add up: each one is reached by a forward (RAW) launch and, where it can carry them, by a Z_STATS and a BWD launch."""
+    import test_gpu_kernels as tg
+    tool = _igemm_plan_tool()
+    rows = tg.igemm_launches()
+    assert {r['name'][:-5] for r in rows if r['dtype'] == 1} == set(tg.IGEMM_FORMS)
+    reached = {}
+    for r in rows:
+        form = _igemm_form(tool.query_row(r)['plan'])
+        if r['dtype'] == 1:
+            assert form == tg.IGEMM_FORMS[r['name'][:-5]], r['name']
+        reached.setdefault((form, r['geom']), set()).add(r['epi'])
+    epis = lambda form, geoms=(0, 1): set().union(*[reached.get((form, g), set()) for g in geoms])
+    for form in ('tile 128x128', 'tile 128x64', 'tile 256x64', 'tile 256x128', 'tile 128x128 split', 'tile 128x64 split', 'direct'):
+        assert epis(form) >= {0, 1, 3}, form
+    for geom in (0, 1):                                    # S2, T2
+        assert epis('patch 128x64', (geom,)) >= {0, 1, 3}, geom
+        for form in ('ring 256x64', 'ring 256x128'):       # (the ring kernel has no RAW epilogue)
+            assert epis(form, (geom,)) >= {1, 3}, (form, geom)
+    assert epis('patch 128x128', (0,)) >= {0}
+    for form in ('patch-tall 256x64', 'patch-pair 128x128'):     # T2 only (the S2 pair form lost to split-K, tall needs T2 / S1)
+        assert epis(form, (1,)) >= {0, 1, 3}, form
+    # the patch kernel's stats epilogues run off the ring kernel's 16 x 16 grid, at the smallest B that plans unsplit
+    for geom, B, C0, N in tg.PATCH_STATS_CASES:
+        for b, want in ((B, 'patch'), (B - 1, 'tile')):
+            r = dict(name='', dtype=1, geom=geom, B=b, Hs=tg.PATCH_HS, Ws=tg.PATCH_WS, C0=C0, C1=0, N=N, epi=1, segs=[N], ks=0)
+            p = tool.query_row(r)['plan']
+            assert p.split()[0] == want and ('nsplit=1 ' in p) == (b == B), p
