@@ -15,7 +15,7 @@ import torch
 
 from . import kernels as K
 from .dc_engine import Act, ConvBNReLU, DCEngine, Head1x1, Op, flag_solo, mark_tail_writers
-from .engine import GraphedStep
+from .trainer import OptimTail
 from ._lib import EPI_ACT, EPI_ADD, GEMM_S1
 
 
@@ -457,22 +457,16 @@ class _GradView:
         self.on_grad_ready = None
 
 
-class AdaBinsTrainer(GraphedStep):
+class AdaBinsTrainer(OptimTail):
     """One fused distillation step: teacher forward, student forward, DistillationLoss, student backward,
     clip_grad_norm_(1.0), AdamW -- train_adabins_distillation.py:445-456 with the loss weights of :179-188."""
 
     def __init__(self, engine, lambda_task=1.0, lambda_response=0.5, lambda_feature=0.3, lambda_bin=0.2,
                  lambda_sparse=0.1, temperature=4.0, optimizer='AdamW', lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=None, clip_norm=1.0, ddp=None):
-        self.engine = engine
-        self.ddp = ddp                    # ddp.GradientAllReducer: one process per GPU, DataParallel semantics
+        self._init_optim(engine, optimizer, lr, betas, eps, weight_decay, clip_norm, ddp)
         self.lambdas = (lambda_task, lambda_response, lambda_feature, lambda_bin, lambda_sparse)
         self.temperature = temperature
-        self.opt_kind = {'AdamW': 0, 'Adam': 1, 'SGD': 2}[optimizer]
-        self.lr, self.betas, self.eps = float(lr), betas, float(eps)
-        self.weight_decay = float((0.01 if optimizer == 'AdamW' else 0.0) if weight_decay is None else weight_decay)
-        self.clip_norm = clip_norm
-        self._ready = False
 
     @classmethod
     def from_criterion(cls, engine, criterion, **kw):
@@ -486,24 +480,18 @@ class AdaBinsTrainer(GraphedStep):
         c = criterion.criterion() if hasattr(criterion, 'get_adaptive_weights') else criterion
         self.lambdas, self.temperature = c.weights(), c.temperature
 
+    # only the student (the suffix of the flat buffers) trains: the teacher is never clipped, stepped or exchanged
+    _optim_offset = property(lambda self: self.engine.train_offset)
+
     def _setup(self, dev):
-        eng = self.engine
-        f64 = dict(dtype=torch.float64, device=dev)
-        self.state = torch.zeros(8, **f64)
-        self.norm_ws = torch.empty(1024 + 8, **f64)
-        self.exp_avg = torch.zeros_like(eng.flat_p)
-        self.exp_avg_sq = torch.zeros_like(eng.flat_p)
-        eng.step_counter = self.state
-        self.bucket_norm = None
-        if self.ddp is not None:
-            # only the student's gradients (the suffix of the flat buffer) are exchanged: the teacher never trains
-            off = eng.train_offset
-            self._ddp_view = _GradView(eng.flat_g[off:])
-            self.ddp.attach(self._ddp_view)
-            eng.on_grad_ready = lambda lo: self._ddp_view.on_grad_ready(max(0, lo - off))
-            if self.clip_norm is not None and eng.flat_g.is_cuda:
-                self.bucket_norm = self.ddp.enable_bucket_norm()
-        self._ready = True
+        super()._setup(dev)
+        self.engine.step_counter = self.state
+
+    def _attach_reducer(self):
+        eng, off = self.engine, self.engine.train_offset
+        self._ddp_view = _GradView(eng.flat_g[off:])
+        self.ddp.attach(self._ddp_view)
+        eng.on_grad_ready = lambda lo: self._ddp_view.on_grad_ready(max(0, lo - off))
 
     def _mean_logits_resized(self, br, S):
         """Spatial mean of the nearest-resized bin logits (the KL term's input when output_size != input size)."""
@@ -518,43 +506,17 @@ class AdaBinsTrainer(GraphedStep):
         wsp = torch.empty(max(K.pool_workspace_bytes(B, S * S, lg.C, 1), 16) // 4, **f32)
         K.pool(n, None, B, S * S, lg.C, 1, 1.0 / (S * S), br.mean_logits, wsp)
 
-    def enable_graph(self, after_steps=3):
-        if self.ddp is not None:
-            raise RuntimeError('the hipGraph step is not combined with the data-parallel reducer (host-side collectives)')
-        super().enable_graph(after_steps)
-
     def _optim_meta(self):
         """Parameters the reference's optimizer holds: filter(requires_grad, model.parameters())
         (train_adabins_distillation.py:371-386); the teacher's (never given a gradient) carry no state."""
         return [(p, off, n) for p, off, n in self.engine.param_meta if p.requires_grad]
 
     def state_dict(self):
-        """'optimizer_state_dict' in torch.optim format (optim_state.py)."""
-        from . import optim_state
-        eng = self.engine
-        if not eng._bound():
-            eng.bind_parameters()
-        step = int(self.state[0].item()) if self._ready else 0
-        sd = optim_state.export_state(self._optim_meta(), eng._view, self.exp_avg if self._ready else None,
-                                      self.exp_avg_sq if self._ready else None, step, self.opt_kind, self.lr, self.betas,
-                                      self.eps, self.weight_decay)
+        sd = super().state_dict()
         for i, (p, off, _) in enumerate(self._optim_meta()):          # teacher parameters: no gradient, no state
-            if off < eng.train_offset:
+            if off < self.engine.train_offset:
                 sd['state'].pop(i, None)
         return sd
-
-    def load_state_dict(self, sd, device):
-        from . import optim_state
-        if not self.engine._bound():
-            self.engine.bind_parameters()
-        self._setup(device)
-        if optim_state.is_torch_format(sd):
-            step, group = optim_state.import_state(sd, self._optim_meta(), self.engine._view, self.exp_avg, self.exp_avg_sq)
-            optim_state.adopt_group(self, group)
-            self.state[0] = float(step)
-        elif 'exp_avg' in sd:
-            step = optim_state.import_legacy_flat(sd, self.engine.param_meta, self.exp_avg, self.exp_avg_sq)
-            self.state[0] = float(step)
 
     def step(self, audio, rgb, gt):
         """audio [B,2,H,W], rgb [B,3,H,W] or None, gt [B,1,H,W] -> (total loss 0-dim device tensor, terms f32[8]).
@@ -565,8 +527,7 @@ class AdaBinsTrainer(GraphedStep):
         eng = self.engine
         m = eng.module
         eng._prepare_branches(audio.shape[0], audio.shape[2], audio.shape[3], audio.device)
-        if not self._ready:
-            self._setup(audio.device)
+        self._ensure_setup(audio.device)
         st, te = eng.branches['audio'], eng.branches['rgb']
         gt = gt.contiguous().float()
         has_t = rgb is not None
@@ -649,15 +610,5 @@ class AdaBinsTrainer(GraphedStep):
             eng.backward_student(dbase, dres, st.dmean, st.dcent_extra, logits_extra=glog)
         if self.ddp is not None:
             self.ddp.finish()
-        off = eng.train_offset
-        p, g = eng.flat_p[off:], eng.flat_g[off:]
-        if self.clip_norm is not None and self.bucket_norm is not None:
-            K.grad_norm_ranges(g, None, self.bucket_norm, float(self.clip_norm), self.state, self.norm_ws)
-        elif self.clip_norm is not None:
-            K.grad_norm(g, float(self.clip_norm), self.state, self.norm_ws)
-        K.optimizer_step(p, g, self.exp_avg[off:], self.exp_avg_sq[off:], self.opt_kind, self.lr, self.betas[0],
-                         self.betas[1], self.eps, self.weight_decay, self.clip_norm is not None, self.state,
-                         bf16_copy=eng.flat_w16[off:] if eng.flat_w16 is not None else None)
-        eng.weights_dirty = True
-        eng.s2_fresh = False            # the teacher half of the bf16 mirror is still valid, but keep the re-cast simple
+        self._apply()
         return eng.terms[6], eng.terms

@@ -12,7 +12,7 @@ import torch
 
 from . import kernels as K
 from .dc_engine import DCEngine, Head1x1, flag_solo, mark_tail_writers
-from .engine import GraphedStep
+from .trainer import OptimTail
 
 
 class BaseResidualEngine(DCEngine):
@@ -153,28 +153,17 @@ def run_base_residual(engine, x, training):
         return engine.run(x, training)
 
 
-class BaseResidualTrainer(GraphedStep):
+class BaseResidualTrainer(OptimTail):
     """One fused step of train_base_residual.py:375-388: forward, BaseResidualLoss (valid = gt > 0), backward,
     clip_grad_norm_(1.0), optimizer."""
 
     def __init__(self, engine, lambda_recon=1.0, lambda_base=1.2, lambda_sparse=0.05, lowpass_kernel=16, use_l1=True,
                  use_silog=False, silog_lambda=0.5, optimizer='AdamW', lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=None, clip_norm=1.0, ddp=None):
-        self.engine = engine
+        self._init_optim(engine, optimizer, lr, betas, eps, weight_decay, clip_norm, ddp)
         self.use_l1 = use_l1
         self.lambda_recon, self.lambda_base, self.lambda_sparse = lambda_recon, lambda_base, lambda_sparse
         self.k, self.use_silog, self.silog_lambda = lowpass_kernel, use_silog, silog_lambda
-        self.opt_kind = {'AdamW': 0, 'Adam': 1, 'SGD': 2}[optimizer]
-        self.lr, self.betas, self.eps = float(lr), betas, float(eps)
-        self.weight_decay = float((0.01 if optimizer == 'AdamW' else 0.0) if weight_decay is None else weight_decay)
-        self.clip_norm = clip_norm
-        self.ddp = ddp                    # ddp.GradientAllReducer: one process per GPU, DataParallel semantics
-        self._ready = False
-
-    def enable_graph(self, after_steps=3):
-        if self.ddp is not None:
-            raise RuntimeError('the hipGraph step is not combined with the data-parallel reducer (host-side collectives)')
-        super().enable_graph(after_steps)
 
     @classmethod
     def from_criterion(cls, engine, criterion, **kw):
@@ -187,71 +176,16 @@ class BaseResidualTrainer(GraphedStep):
         c = getattr(criterion, 'base_loss', criterion)
         self.set_weights(c.lambda_recon, c.lambda_base)
 
-    def load_state_dict(self, sd, device):
-        """Restore a torch.optim state dict (optim_state.py; the 'optimizer_state_dict' entry of the checkpoints written
-        by train_dc._run or by the reference's torch optimizer); round 1's flat layout is re-sliced per parameter or rejected."""
-        from . import optim_state
-        if not self.engine._bound():
-            self.engine.bind_parameters()
-        self._setup_optimizer(torch.device(device))
-        if optim_state.is_torch_format(sd):
-            step, group = optim_state.import_state(sd, self.engine.param_meta, self.engine._view, self.exp_avg,
-                                                   self.exp_avg_sq)
-            optim_state.adopt_group(self, group)
-            self.state[0] = float(step)
-        elif 'exp_avg' in sd:
-            step = optim_state.import_legacy_flat(sd, self.engine.param_meta, self.exp_avg, self.exp_avg_sq)
-            self.state[0] = float(step)
-
-    def _setup_optimizer(self, dev):
-        if getattr(self, '_opt_ready', False):
-            return
-        eng = self.engine
-        self.state = torch.zeros(8, dtype=torch.float64, device=dev)
-        self.exp_avg, self.exp_avg_sq = torch.zeros_like(eng.flat_p), torch.zeros_like(eng.flat_p)
-        self._opt_ready = True
-
     def set_weights(self, lambda_recon, lambda_base):
         """AdaptiveBaseResidualLoss.set_epoch (utils_base_residual_loss.py:210-229) result."""
         self.lambda_recon, self.lambda_base = lambda_recon, lambda_base
 
-    _SCRATCH = ('lstats', 'bstats', 'loss_ws', 'norm_ws', 'recon', 'terms', 'struct', 'gfinal', 'dbase', 'dres')
-
-    def _setup(self, pred):
-        """Loss / gradient scratch of one batch shape.  Every shape keeps its own set for the trainer's lifetime: a captured
-        hipGraph holds raw pointers into the set it was captured with, and an eager step on another shape in between (a
-        ragged last batch) must not free or rebind those buffers (round-2 advisor finding)."""
-        eng, dev = self.engine, pred.device
-        f64, f32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.float32, device=dev)
-        self._setup_optimizer(dev)
-        sets = self.__dict__.setdefault('_scratch_sets', {})
-        key = tuple(pred.shape)
-        if key not in sets:
-            sets[key] = dict(lstats=torch.zeros(4, **f64), bstats=torch.zeros(4, **f64),
-                             loss_ws=torch.empty(4096 + 8, **f64), norm_ws=torch.empty(1024 + 8, **f64),
-                             recon=torch.zeros(1, **f32), terms=torch.zeros(4, **f32),
-                             struct=torch.empty_like(pred), gfinal=torch.empty_like(pred),
-                             dbase=torch.empty_like(pred), dres=torch.empty_like(pred))
-        for name in self._SCRATCH:
-            setattr(self, name, sets[key][name])
-        if not self._ready:
-            self.bucket_norm = None
-            if self.ddp is not None:
-                self.ddp.attach(eng)
-                if self.clip_norm is not None and eng.flat_g.is_cuda:
-                    self.bucket_norm = self.ddp.enable_bucket_norm()
-        self._ready = True
-
-    def state_dict(self):
-        from . import optim_state
-        eng = self.engine
-        if not eng._bound():
-            eng.bind_parameters()
-        ready = getattr(self, '_opt_ready', False)
-        step = int(self.state[0].item()) if ready else 0
-        return optim_state.export_state(eng.param_meta, eng._view, self.exp_avg if ready else None,
-                                        self.exp_avg_sq if ready else None, step, self.opt_kind, self.lr, self.betas,
-                                        self.eps, self.weight_decay)
+    def _new_scratch(self, pred):
+        """Loss / gradient scratch of one batch shape (lstats, bstats, loss_ws, recon, terms, struct, gfinal, dbase, dres)."""
+        f64, f32 = dict(dtype=torch.float64, device=pred.device), dict(dtype=torch.float32, device=pred.device)
+        return dict(lstats=torch.zeros(4, **f64), bstats=torch.zeros(4, **f64), loss_ws=torch.empty(4096 + 8, **f64),
+                    recon=torch.zeros(1, **f32), terms=torch.zeros(4, **f32), struct=torch.empty_like(pred),
+                    gfinal=torch.empty_like(pred), dbase=torch.empty_like(pred), dres=torch.empty_like(pred))
 
     def step(self, x, gt):
         """Returns (total loss 0-dim device tensor, terms f32[4] = weighted recon, mean|base-struct|, mean|res|, total)."""
@@ -261,8 +195,8 @@ class BaseResidualTrainer(GraphedStep):
         eng = self.engine
         base, resid, final = eng.forward_net(x, True)
         gt = gt.contiguous().float()
-        if not self._ready or self.struct.shape != final.shape:
-            self._setup(final)
+        self._ensure_setup(final.device)
+        vars(self).update(self._shape_scratch(tuple(final.shape), lambda: self._new_scratch(final)))
         K.lowpass(gt, self.k, self.struct, eng.workspace)
         from .utils_base_residual_loss import recon_criterion
         crit, mm = recon_criterion(self.use_l1, self.use_silog)   # weighted SIlog / L1 (Combined, one weight) or masked MSE
@@ -284,13 +218,5 @@ class BaseResidualTrainer(GraphedStep):
         eng.backward_net(self.dbase, self.dres)
         if self.ddp is not None:
             self.ddp.finish()
-        if self.clip_norm is not None and self.bucket_norm is not None:
-            K.grad_norm_ranges(eng.flat_g, None, self.bucket_norm, float(self.clip_norm), self.state, self.norm_ws)
-        elif self.clip_norm is not None:
-            K.grad_norm(eng.flat_g, float(self.clip_norm), self.state, self.norm_ws)
-        K.optimizer_step(eng.flat_p, eng.flat_g, self.exp_avg, self.exp_avg_sq, self.opt_kind, self.lr, self.betas[0],
-                         self.betas[1], self.eps, self.weight_decay, self.clip_norm is not None, self.state,
-                         bf16_copy=eng.flat_w16)
-        eng.weights_dirty = True
-        eng.s2_fresh = eng.flat_w16 is not None
+        self._apply()
         return self.terms[3], self.terms

@@ -144,8 +144,7 @@ class CVAETrainer(FusedTrainer):
 
     def _step_impl(self, audio, gt):
         eng = self.engine
-        if not self._ready or self._flat_id != (eng.flat_p.data_ptr() if eng.flat_p is not None else None):
-            self._setup(audio.device)
+        self._ensure_setup(audio.device)
         eng.step_counter, eng.g_kl, eng.loss_acc = self.state, self.kl_w, self.loss
         try:
             return super()._step_impl(audio, gt)

@@ -829,8 +829,9 @@ class DCEngine(FlatParamEngine):
                 off = self.param_meta[idx][1]
                 _lib.record_py(lambda: self.on_grad_ready(off))
 
-    def backward(self, gout):
-        """gout: d loss / d output, f32 [B,1,H,W].  Fills flat_g (all parameters)."""
+    def backward(self, gout, fused_norm=False, dz_ready=False):
+        """gout: d loss / d output, f32 [B,1,H,W].  Fills flat_g (all parameters).  ``fused_norm`` / ``dz_ready`` are
+        the U-Net engine's options (this one offers neither: supports_fused_norm, dz_target) and are ignored."""
         for a in self.acts:
             a.written = False
         self._final = set(id(p) for p, _, _ in self.param_meta if not p.requires_grad)

@@ -1,4 +1,4 @@
-"""Fused U-Net pipeline on libadn kernels: forward, backward, loss, clip, optimizer.
+"""Fused U-Net pipeline on libadn kernels: forward and backward (loss, clip and optimizer: trainer.FusedTrainer).
 
 This is the MI355X-side replacement of what PyTorch dispatches for the reference's
 ``model(audio)`` / ``loss.backward()`` / ``clip_grad_norm_`` / ``optimizer.step()``
@@ -572,258 +572,4 @@ def run_unet(engine, x, training):
         return engine.forward(x, training).clone()
 
 
-class GraphedStep:
-    """Launch-overhead removal shared by the fused trainers: after ``after_steps`` eager steps the whole step (a few
-    hundred libadn launches, nothing synchronising with the host) is captured into ONE hipGraph over static input
-    buffers and replayed.  Subclasses implement ``_step_impl(*inputs)`` (inputs may be None) and return device
-    tensors that stay valid across replays."""
-    _graph = None
-    _graph_after = None
-    _calls = 0
-
-    def enable_graph(self, after_steps=3):
-        self._graph_after = after_steps
-
-    def _graphed(self, *inputs):
-        self._calls += 1
-        if self._graph is not None:
-            if any((b is None) != (t is None) or (b is not None and b.shape != t.shape) for b, t in zip(self._g_in, inputs)):
-                return self._step_impl(*inputs)          # another batch shape: eager, on that shape's own buffer set
-            for buf, t in zip(self._g_in, inputs):
-                if buf is not None:
-                    buf.copy_(t)
-            self._graph.replay()
-            self.engine.weights_dirty, self.engine.s2_fresh = self._post_flags
-            return self._g_out
-        if self._graph_after is not None and self._calls > self._graph_after:
-            self._g_in = [None if t is None else t.contiguous().float().clone() for t in inputs]
-            torch.cuda.synchronize()
-            self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
-                self._g_out = self._step_impl(*self._g_in)
-            self.engine.pin_buffers()                    # the graph holds raw pointers into this shape's buffer set
-            # the replayed optimizer step changes the weights behind Python's back: restore the engine's
-            # "operands are stale" flags after every replay (an eval forward in between clears them)
-            self._post_flags = (self.engine.weights_dirty, self.engine.s2_fresh)
-            self._graph.replay()            # capture only records: run the step once for real
-            return self._g_out
-        return self._step_impl(*inputs)
-
-
-class FusedTrainer:
-    """One fused training step: forward + masked loss + backward + (all-reduce) + clip + optimizer.
-
-    Mirrors the hot loop of /root/reference/train.py:633-693 (and train_binaural_attention.py:394-433 when
-    ``clip_norm`` is None and ``mask_mode`` is 'gt0'; train_rgb_depth.py:355-362 with criterion 'DepthLoss',
-    where l1_weight / silog_weight carry lambda_l1 / lambda_smooth).  ``engine`` is a UNetEngine or a DCEngine
-    (both expose forward / backward / flat_p / flat_g / flat_w16).  Everything stays on device; ``step`` returns the
-    loss as a 0-dim device tensor (call .item() to reproduce the reference's per-step host sync).
-    """
-    CRIT = {'L1': 0, 'SIlog': 1, 'Combined': 2, 'DepthLoss': 3}
-    OPT = {'AdamW': 0, 'Adam': 1, 'SGD': 2}
-
-    def __init__(self, engine, criterion='Combined', l1_weight=0.5, silog_weight=0.5, silog_lambda=0.5,
-                 max_depth=30.0, optimizer='AdamW', lr=0.002, betas=(0.9, 0.999), eps=1e-8, weight_decay=None,
-                 clip_norm=1.0, mask_mode='ne0', ddp=None):
-        self.engine = engine
-        self.criterion = self.CRIT[criterion]
-        self.l1_weight, self.silog_weight, self.silog_lambda = float(l1_weight), float(silog_weight), float(silog_lambda)
-        self.scale = float(max_depth) if engine.depth_norm else 1.0       # train.py:649-652
-        self.opt_kind = self.OPT[optimizer]
-        self.lr, self.betas, self.eps = float(lr), betas, float(eps)
-        if weight_decay is None:                                           # torch defaults (train.py passes only lr)
-            weight_decay = 0.01 if optimizer == 'AdamW' else 0.0
-        self.weight_decay = float(weight_decay)
-        self.clip_norm = clip_norm
-        self.mask_mode = 0 if mask_mode == 'ne0' else 1
-        self.ddp = ddp
-        self._ready = False
-        self._graph = None
-        self._graph_after = None
-        self._plan = None
-        self._plan_after = None
-        self._calls = 0
-        self._gout_valid, self._last_pred_gt = True, None
-
-    def enable_launch_plan(self, after_steps=3):
-        """Record the step's launches once (after ``after_steps`` eager steps) and replay the prebuilt ctypes
-        calls afterwards: the low-overhead eager mode used with the data-parallel reducer, whose collectives
-        stay ordinary torch.distributed calls inside the plan."""
-        self._plan_after = after_steps
-
-    def enable_graph(self, after_steps=3):
-        """Capture the whole step into one hipGraph after ``after_steps`` eager steps (fixed batch shape).
-
-        Every launch of the step is on the current stream and nothing synchronises with the host, so the
-        ~140 kernel launches replay as one graph launch.  Not combined with the data-parallel reducer.
-        """
-        if self.ddp is not None:
-            raise RuntimeError('graph capture of the step is only wired for single-process training')
-        self._graph_after = after_steps
-
-    def _setup(self, dev):
-        eng = self.engine
-        if not eng._bound():
-            eng.bind_parameters()
-        f64 = dict(dtype=torch.float64, device=dev)
-        self.stats = torch.zeros(4, **f64)
-        self.state = torch.zeros(8, **f64)
-        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.loss_ws = torch.empty(4096 + 8, **f64)
-        self.norm_ws = torch.empty(1024 + 8, **f64)
-        self.exp_avg = torch.zeros_like(eng.flat_p)
-        self.exp_avg_sq = torch.zeros_like(eng.flat_p)
-        self.gout = None
-        self._gout_sets = {}
-        self._flat_id = eng.flat_p.data_ptr()
-        self.bucket_norm = None
-        if self.ddp is not None:
-            self.ddp.attach(eng)
-            if self.clip_norm is not None and eng.flat_g.is_cuda:
-                self.bucket_norm = self.ddp.enable_bucket_norm()      # sums of squares per reduced bucket (ddp.finish)
-        self._ready = True
-
-    def state_dict(self):
-        """The checkpoint's 'optimizer' / 'optimizer_state_dict' entry in ``torch.optim`` format (optim_state.py): what
-        ``torch.optim.AdamW(model.parameters(), ...).state_dict()`` would hold after the same steps, so the reference's
-        ``optimizer.load_state_dict`` (train_binaural_attention.py:361) reads it and vice versa."""
-        from . import optim_state
-        eng = self.engine
-        if not eng._bound():
-            eng.bind_parameters()
-        step = int(self.state[0].item()) if self._ready else 0
-        return optim_state.export_state(eng.param_meta, eng._view, self.exp_avg if self._ready else None,
-                                        self.exp_avg_sq if self._ready else None, step, self.opt_kind, self.lr,
-                                        self.betas, self.eps, self.weight_decay)
-
-    def load_state_dict(self, sd, device):
-        """Restore a ``torch.optim`` state dict (written by this class or by the reference's torch optimizer over the
-        same parameters); the flat layout of round 1 ('exp_avg' / 'exp_avg_sq' / 'step')
-        is re-sliced parameter by parameter (its alignment was 4 elements, today's is 8) or rejected."""
-        from . import optim_state
-        self._setup(device)
-        if optim_state.is_torch_format(sd):
-            step, group = optim_state.import_state(sd, self.engine.param_meta, self.engine._view, self.exp_avg,
-                                                   self.exp_avg_sq)
-            optim_state.adopt_group(self, group)
-            self._set_step(step)
-        elif 'exp_avg' in sd:
-            step = optim_state.import_legacy_flat(sd, self.engine.param_meta, self.exp_avg, self.exp_avg_sq)
-            self._set_step(step)
-
-    def _set_step(self, step):
-        """state = [step, 1 - beta1^step, 1 - beta2^step, ...] (adn_optimizer_step advances all three)."""
-        self.state[0] = float(step)
-        self.state[1] = 1.0 - self.betas[0] ** step
-        self.state[2] = 1.0 - self.betas[1] ** step
-
-    def step(self, audio, gt):
-        self._calls += 1
-        captured = self._plan is not None or self._graph is not None
-        if captured and (audio.shape != self._g_audio.shape or gt.shape != self._g_gt.shape):
-            return self._step_impl(audio, gt)            # another batch shape: eager, on that shape's own buffer set
-        if self._plan is not None:
-            self._g_audio.copy_(audio)
-            self._g_gt.copy_(gt)
-            _lib.replay(self._plan)
-            self.engine.weights_dirty, self.engine.s2_fresh = self._post_flags
-            return self._g_out
-        if self._plan_after is not None and self._calls > self._plan_after and self._ready:
-            self._g_audio, self._g_gt = audio.clone(), gt.contiguous().float().clone()
-            _lib.RECORD = []
-            try:
-                self._g_out = self._step_impl(self._g_audio, self._g_gt)
-                self._plan = _lib.RECORD
-            finally:
-                _lib.RECORD = None
-            self.engine.pin_buffers()                    # the plan holds raw pointers into this shape's buffer set
-            self._post_flags = (self.engine.weights_dirty, self.engine.s2_fresh)
-            return self._g_out
-        if self._graph is not None:
-            self._g_audio.copy_(audio)
-            self._g_gt.copy_(gt)
-            self._graph.replay()
-            self.engine.weights_dirty, self.engine.s2_fresh = self._post_flags
-            return self._g_out
-        if self._graph_after is not None and self._calls > self._graph_after and self._ready:
-            self._g_audio, self._g_gt = audio.clone(), gt.contiguous().float().clone()
-            torch.cuda.synchronize()
-            self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
-                self._g_out = self._step_impl(self._g_audio, self._g_gt)
-            self.engine.pin_buffers()                    # the graph holds raw pointers into this shape's buffer set
-            self._post_flags = (self.engine.weights_dirty, self.engine.s2_fresh)
-            self._graph.replay()            # capture only records: run the step once for real
-            return self._g_out
-        return self._step_impl(audio, gt)
-
-    def loss_gradient(self):
-        """d loss / d prediction of the last step (diagnostics, tests).  When the fused loss kernel wrote the gradient of
-        the output's PRE-activation instead (adn_loss_finish_dz), it is recomputed here from that step's statistics."""
-        if not self._gout_valid:
-            pred, gt = self._last_pred_gt
-            K.loss_finish(pred, gt, self.scale, self.mask_mode, 1e-6, self.stats, self.criterion, self.l1_weight,
-                          self.silog_weight, self.silog_lambda, None, self.gout)
-            self._gout_valid = True
-        return self.gout
-
-    def _step_impl(self, audio, gt):
-        eng = self.engine
-        if not self._ready or self._flat_id != (eng.flat_p.data_ptr() if eng.flat_p is not None else None):
-            self._setup(audio.device)
-        pred = eng.forward(audio, True)
-        gt = gt.contiguous().float()
-        dz_ready = False
-        # loss-gradient scratch PER BATCH SHAPE, never freed: a captured hipGraph / launch plan holds its raw pointer, and an
-        # eager step on another batch shape in between (ragged last batch) must not hand that block back to the allocator
-        key = tuple(pred.shape)
-        if key not in self._gout_sets:
-            self._gout_sets[key] = torch.empty_like(pred)
-        self.gout = self._gout_sets[key]
-        if self.criterion == 3:       # DepthLoss: unmasked L1 + total variation (train_rgb_depth.py:43-87)
-            K.l1tv_stats(pred, gt, self.stats, self.loss_ws)
-            if self.ddp is not None:
-                _lib.record_py(lambda: self.ddp.all_reduce_loss_stats(self.stats))
-            K.l1tv_finish(pred, gt, self.stats, self.ddp.world_size if self.ddp is not None else 1, self.l1_weight,
-                          self.silog_weight, self.loss, self.gout)
-        else:
-            K.loss_stats(pred, gt, self.scale, self.mask_mode, 1e-6, self.stats, self.loss_ws)
-            if self.ddp is not None:      # one global-batch loss, as under DataParallel
-                _lib.record_py(lambda: self.ddp.all_reduce_loss_stats(self.stats))
-            # U-Net with the thin last layer: the loss kernel writes d loss / d pre-activation and the bias gradient itself
-            target = eng.dz_target() if (hasattr(eng, 'dz_target') and self.criterion <= 2) else None
-            if target is not None:
-                dz, bias_grad, final_act = target
-                K.loss_finish_dz(pred, gt, self.scale, self.mask_mode, 1e-6, self.stats, self.criterion, self.l1_weight,
-                                 self.silog_weight, self.silog_lambda, self.loss, dz, final_act, bias_grad, self.loss_ws)
-                dz_ready = True
-            else:
-                K.loss_finish(pred, gt, self.scale, self.mask_mode, 1e-6, self.stats, self.criterion, self.l1_weight,
-                              self.silog_weight, self.silog_lambda, self.loss, self.gout)
-        if self.ddp is not None:
-            _lib.record_py(self.ddp.begin_backward)
-        # single process: the weight-gradient kernels leave their share of the total norm behind (no pass over flat_g);
-        # under the reducer the norm is that of the all-reduced gradients, taken afterwards
-        fused = (self.clip_norm is not None and self.ddp is None and getattr(eng, 'supports_fused_norm', False)
-                 and eng.sq_all is not None)
-        self._gout_valid, self._last_pred_gt = not dz_ready, (pred, gt)
-        if dz_ready:
-            eng.backward(self.gout, fused_norm=fused, dz_ready=True)
-        elif fused:
-            eng.backward(self.gout, fused_norm=True)
-        else:
-            eng.backward(self.gout)
-        if self.ddp is not None:
-            _lib.record_py(self.ddp.finish)
-        if fused:
-            K.grad_norm_ranges(eng.flat_g, eng.norm_ranges, eng.sq_all, float(self.clip_norm), self.state, self.norm_ws)
-        elif self.clip_norm is not None and self.bucket_norm is not None:
-            K.grad_norm_ranges(eng.flat_g, None, self.bucket_norm, float(self.clip_norm), self.state, self.norm_ws)
-        elif self.clip_norm is not None:
-            K.grad_norm(eng.flat_g, float(self.clip_norm), self.state, self.norm_ws)
-        K.optimizer_step(eng.flat_p, eng.flat_g, self.exp_avg, self.exp_avg_sq, self.opt_kind, self.lr,
-                         self.betas[0], self.betas[1], self.eps, self.weight_decay, self.clip_norm is not None,
-                         self.state, bf16_copy=eng.flat_w16)
-        eng.weights_dirty = True
-        eng.s2_fresh = eng.flat_w16 is not None      # the optimizer just refreshed the bf16 S2 operands
-        return self.loss[0], pred
+from .trainer import FusedTrainer, GraphedStep  # noqa: E402,F401  (the trainer classes live in trainer.py)

@@ -19,6 +19,14 @@ def _align(n, a=8):       # 8 elements: 32-byte f32 slices, 16-byte slices of th
 class FlatParamEngine:
     """Parameter plumbing of an engine; subclasses set ``module``, ``dtype`` and ``model_name``."""
     model_name = 'model'
+    # optional features a trainer asks for by name (UNetEngine has them); sq_all / norm_ranges are per-shape state
+    supports_fused_norm = False                     # backward(fused_norm=True) leaves sums of dW^2 in sq_all
+    sq_all = None
+    norm_ranges = None
+
+    def dz_target(self):
+        """Where a loss kernel may write d loss / d pre-activation of the output itself; None: hand backward gout."""
+        return None
 
     def _init_flat(self):
         self.flat_p = None

@@ -285,3 +285,101 @@ def test_igemm_gpu_test_shapes_reach_the_forms_they_name():
             r = dict(name='', dtype=1, geom=geom, B=b, Hs=tg.PATCH_HS, Ws=tg.PATCH_WS, C0=C0, C1=0, N=N, epi=1, segs=[N], ks=0)
             p = tool.query_row(r)['plan']
             assert p.split()[0] == want and ('nsplit=1 ' in p) == (b == B), p
+
+
+def test_launch_plan_capture_and_replay_state_machine():
+    """GraphedStep's launch-plan path on CPU tensors: ``after_steps`` eager calls, one recording call, replays over the
+    static input buffers with the engine flags restored, eager steps for any other input signature, and re-arming."""
+    from audio_depth_estimation_amd import _lib
+    from audio_depth_estimation_amd.trainer import GraphedStep
+
+    class Engine:
+        weights_dirty, s2_fresh, pins = False, False, 0
+
+        def pin_buffers(self):
+            self.pins += 1
+
+    class Step(GraphedStep):
+        def __init__(self):
+            self.engine, self.out, self.impl_calls = Engine(), torch.zeros(3), 0
+
+        def _step_impl(self, a, b, c):
+            self.impl_calls += 1
+
+            def work():           # out = sum(a) + (sum(b) if given) + 10 * sum(c): everything goes through record_py
+                self.out.fill_(float(a.sum()) + (float(b.sum()) if b is not None else 0.0) + 10.0 * float(c.sum()))
+            _lib.record_py(work)
+            self.engine.weights_dirty, self.engine.s2_fresh = True, True
+            return self.out
+
+    def value(a, b, c):
+        return float(a.sum()) + (float(b.sum()) if b is not None else 0.0) + 10.0 * float(c.sum())
+
+    mk = lambda seed, n=4: torch.arange(n, dtype=torch.float32) + seed
+    for with_b in (True, False):                     # a None input is part of the captured signature
+        t, after = Step(), 2
+        eng = t.engine
+        t._plan_after = after
+        for i in range(after):                       # exactly ``after_steps`` eager calls
+            a, b, c = mk(i), (mk(i + 1) if with_b else None), mk(i + 2)
+            assert float(t._graphed(a, b, c)[0]) == value(a, b, c)
+            assert t._plan is None and t.impl_calls == i + 1 and eng.pins == 0
+        a, b, c = mk(7), (mk(8) if with_b else None), mk(9).double()       # the recording call; f64 is stored as f32
+        out = t._graphed(a, b, c)
+        assert out is t.out and float(out[0]) == value(a, b, c)
+        assert t.impl_calls == after + 1 and eng.pins == 1 and _lib.RECORD is None
+        assert len(t._plan) == 1 and t._plan[0][0] is None and t._plan[0][2] == 'py'
+        assert [None if g is None else g.dtype for g in t._g_in] == [torch.float32, torch.float32 if with_b else None,
+                                                                     torch.float32]
+        assert t._g_in[0] is not a and (t._g_in[1] is None) == (not with_b)
+        assert t._post_flags == (True, True)
+        bufs = list(t._g_in)
+        for i in range(3):                           # replays: inputs copied into the static buffers, same output object
+            eng.weights_dirty, eng.s2_fresh = False, False          # (an eval forward in between clears the flags)
+            a, b, c = mk(20 + i), (mk(30 + i) if with_b else None), mk(40 + i)
+            out = t._graphed(a, b, c)
+            assert out is t.out and float(out[0]) == value(a, b, c)
+            assert t.impl_calls == after + 1                         # nothing ran but the plan
+            assert all(g is h for g, h in zip(t._g_in, bufs)) and torch.equal(t._g_in[0], a) and torch.equal(t._g_in[2], c)
+            assert (eng.weights_dirty, eng.s2_fresh) == (True, True)
+        # another batch shape, or None where a tensor was captured (and the reverse): eager, the plan stays
+        plan, n = t._plan, t.impl_calls
+        odd = [(mk(1, 5), (mk(2, 5) if with_b else None), mk(3, 5)),
+               (mk(1), (None if with_b else mk(2)), mk(3))]
+        for a, b, c in odd:
+            eng.weights_dirty = False
+            assert float(t._graphed(a, b, c)[0]) == value(a, b, c)
+            n += 1
+            assert t.impl_calls == n and t._plan is plan and eng.pins == 1
+            assert all(g is h for g, h in zip(t._g_in, bufs)) and not torch.equal(t._g_in[0][:4], a[:4])
+        a, b, c = mk(50), (mk(51) if with_b else None), mk(52)
+        assert float(t._graphed(a, b, c)[0]) == value(a, b, c) and t.impl_calls == n      # the plan still replays
+        # dropping the plan: eager again, and it can be re-armed
+        t._plan, t._plan_after = None, None
+        for i in range(2):
+            a, b, c = mk(60 + i), (mk(61 + i) if with_b else None), mk(62 + i)
+            assert float(t._graphed(a, b, c)[0]) == value(a, b, c)
+            n += 1
+            assert t.impl_calls == n and t._plan is None
+        t._plan_after = 0
+        a, b, c = mk(70, 6), (mk(71, 6) if with_b else None), mk(72, 6)      # re-armed on another shape
+        assert float(t._graphed(a, b, c)[0]) == value(a, b, c)
+        assert t.impl_calls == n + 1 and t._plan is not None and t._plan is not plan and eng.pins == 2
+        assert t._g_in[0].shape == (6,) and t._g_in[0] is not bufs[0]
+        a, b, c = mk(80, 6), (mk(81, 6) if with_b else None), mk(82, 6)
+        assert float(t._graphed(a, b, c)[0]) == value(a, b, c) and t.impl_calls == n + 1
+
+    class Gated(Step):               # the overridable capture gate: an armed trainer stays eager until it opens
+        ok = False
+
+        def _capture_ok(self):
+            return self.ok
+
+    t = Gated()
+    t._plan_after = 0
+    for i in range(2):
+        t._graphed(mk(i), None, mk(i))
+        assert t._plan is None and t.impl_calls == i + 1
+    t.ok = True
+    t._graphed(mk(5), None, mk(5))
+    assert t._plan is not None and t.impl_calls == 3 and t.engine.pins == 1
