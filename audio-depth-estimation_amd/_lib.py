@@ -83,6 +83,17 @@ class AdnDistillSmall(C.Structure):
     ]
 
 
+class AdnCoarseLoss(C.Structure):
+    _fields_ = [
+        ('logits', c_void_p), ('dtype', c_int32), ('nb', c_int32), ('ld', c_int32), ('ce_mode', c_int32),
+        ('pixels', c_int64), ('pixels_global', c_int64),
+        ('centers', c_void_p), ('bins', c_void_p), ('gt', c_void_p), ('n_valid', c_void_p),
+        ('sigma', c_float), ('gamma', c_float), ('ce_weight', c_float), ('reg_weight', c_float),
+        ('depth', c_void_p), ('argmax', c_void_p), ('dlogits', c_void_p),
+        ('workspace', c_void_p), ('workspace_bytes', c_int64),
+    ]
+
+
 # name -> (restype, argtypes).  Must list every symbol include/adn.h declares
 # (tests/test_abi.py cross-checks this table against the header and the built library).
 _PROTOS = {
@@ -238,6 +249,12 @@ _PROTOS = {
     'adn_vae_bwd': (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    'adn_coarse_targets_workspace_bytes': (c_int64, [c_int64]),
+    'adn_coarse_targets': (C.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    'adn_coarse_loss_workspace_bytes': (c_int64, [c_int64]),
+    'adn_coarse_loss': (C.c_int, [C.POINTER(AdnCoarseLoss), c_void_p]),
+    'adn_coarse_loss_finish': (C.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p,
+                                         c_void_p]),
 }
 
 _lib = None

@@ -139,3 +139,21 @@ class GpuImageTransform:
         out = torch.empty(frames.shape[0], 3, self.size, self.size, dtype=torch.float32, device=frames.device)
         K.image_prepare(frames, self.size, out)
         return out
+
+
+def compute_bins(n_bins, bin_mode='linear', depth_min=None, depth_max=30.0, sid_alpha=0.6):
+    """(bin_edges f32 [n_bins + 1], bin_centers f32 [n_bins]) of BinnedDepthDataset._compute_bins
+    (SparseDepth_Dataset.py:284-303): float64 numpy arithmetic rounded to f32 at the end; a falsy ``depth_min`` means
+    0.1 m (:274).  'sid' is the spacing-increasing discretisation of DORN with exponent ``sid_alpha``."""
+    depth_min = depth_min if depth_min else 0.1
+    if bin_mode == 'linear':
+        edges = np.linspace(depth_min, depth_max, n_bins + 1)
+    elif bin_mode == 'log':
+        edges = np.logspace(np.log10(depth_min), np.log10(depth_max), n_bins + 1)
+    elif bin_mode == 'sid':
+        t = np.linspace(0, 1, n_bins + 1)
+        edges = depth_min * (depth_max / depth_min) ** (t ** sid_alpha)
+    else:
+        raise ValueError(f"Unknown bin_mode: {bin_mode}")
+    centers = (edges[:-1] + edges[1:]) / 2
+    return torch.from_numpy(edges.astype(np.float32)), torch.from_numpy(centers.astype(np.float32))

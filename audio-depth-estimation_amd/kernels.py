@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import AdnAttnDesc, AdnDistillSmall  # noqa: E402
+from ._lib import AdnAttnDesc, AdnCoarseLoss, AdnDistillSmall  # noqa: E402
 from ._lib import (ADN_BF16, ADN_F32, EPI_ACT, EPI_ADD, EPI_BWD, EPI_FINAL, EPI_RAW, EPI_Z_STATS, GEMM_S1, GEMM_S2, GEMM_T2,
                    AdnEpiSeg, AdnIgemmDesc, AdnMx8ConvDesc, AdnWgradDesc, ptr)
 
@@ -1018,3 +1018,63 @@ def baseres_grad(base, resid, strct, gt, gfinal, max_depth, stats, lbase, lspars
     _dev(base, resid, strct, gt, gfinal, stats, dbase, dres)
     _lib.call('adn_baseres_grad', ptr(base), ptr(resid), ptr(strct), ptr(gt), ptr(gfinal), base.numel(), float(max_depth),
               ptr(stats), float(lbase), float(lsparse), ptr(dbase), ptr(dres), _stream())
+
+
+# ---- coarse-depth classification family (csrc/coarse.hip) ---------------------------------------------------------
+CE_MODES = {'soft': 0, 'focal': 1, 'ce': 2}
+
+
+def coarse_targets_workspace_bytes(n):
+    return _lib.load().adn_coarse_targets_workspace_bytes(n)
+
+
+def coarse_targets(depth, edges, bins, stats, workspace):
+    """depth f32 [n]; edges f32 = the n_bins - 1 interior bin edges; bins int32 [n] or None (valid count alone);
+    stats f64[>= 1]: stats[0] = count of depth > 0."""
+    _dev(depth, edges, bins, stats, workspace)
+    if depth.dtype != torch.float32 or not depth.is_contiguous():
+        raise RuntimeError('coarse_targets: depth must be contiguous float32')
+    nb = 0
+    if bins is not None:
+        if edges is None or bins.dtype != torch.int32 or bins.numel() != depth.numel() or edges.dtype != torch.float32:
+            raise RuntimeError('coarse_targets: bins must be int32 with one entry per depth value, edges float32')
+        nb = edges.numel() + 1
+    _lib.call('adn_coarse_targets', ptr(depth), depth.numel(), ptr(edges), nb, ptr(bins), ptr(stats), ptr(workspace),
+              _nbytes(workspace), _stream())
+
+
+def coarse_loss_workspace_bytes(pixels):
+    return _lib.load().adn_coarse_loss_workspace_bytes(pixels)
+
+
+def coarse_loss(logits, nb, centers, depth, bins=None, gt=None, n_valid=None, pixels_global=None, ce_mode=0, sigma=2.0,
+                gamma=2.0, ce_weight=1.0, reg_weight=0.5, argmax=None, dlogits=None, workspace=None):
+    """logits [..., ld] (bf16 / f32, ld >= nb), centers f32 [nb], depth f32 [pixels] out; see adn_coarse_loss."""
+    ld = logits.shape[-1]
+    pixels = logits.numel() // ld
+    _dev(logits, centers, depth, bins, gt, n_valid, argmax, dlogits, workspace)
+    for name, t, dt in (('centers', centers, torch.float32), ('depth', depth, torch.float32), ('bins', bins, torch.int32),
+                        ('gt', gt, torch.float32), ('n_valid', n_valid, torch.float64), ('argmax', argmax, torch.int32),
+                        ('dlogits', dlogits, logits.dtype)):
+        if t is not None and (t.dtype != dt or not t.is_contiguous()):
+            raise RuntimeError(f'coarse_loss: {name} must be contiguous {dt}')
+    for name, t in (('depth', depth), ('bins', bins), ('gt', gt), ('argmax', argmax)):
+        if t is not None and t.numel() != pixels:
+            raise RuntimeError(f'coarse_loss: {name} has {t.numel()} elements for {pixels} pixels')
+    if centers.numel() != nb or not logits.is_contiguous() or (dlogits is not None and dlogits.shape != logits.shape):
+        raise RuntimeError('coarse_loss: centers must hold n_bins values; logits / dlogits contiguous and same shape')
+    d = AdnCoarseLoss()
+    d.logits, d.dtype, d.nb, d.ld, d.ce_mode = ptr(logits), dtype_code(logits.dtype), nb, ld, int(ce_mode)
+    d.pixels, d.pixels_global = pixels, int(pixels_global if pixels_global is not None else pixels)
+    d.centers, d.bins, d.gt, d.n_valid = ptr(centers), ptr(bins), ptr(gt), ptr(n_valid)
+    d.sigma, d.gamma, d.ce_weight, d.reg_weight = float(sigma), float(gamma), float(ce_weight), float(reg_weight)
+    d.depth, d.argmax, d.dlogits = ptr(depth), ptr(argmax), ptr(dlogits)
+    d.workspace, d.workspace_bytes = ptr(workspace), (_nbytes(workspace) if workspace is not None else 0)
+    _lib.call('adn_coarse_loss', C.byref(d), _stream())
+
+
+def coarse_loss_finish(workspace, pixels, sums, n_valid, pixels_global, ce_weight, reg_weight, terms):
+    """workspace None: sums f64[2] are taken as given (all-reduced); terms f32[3] = ce, regression, total (or None)."""
+    _dev(workspace, sums, n_valid, terms)
+    _lib.call('adn_coarse_loss_finish', ptr(workspace), int(pixels), ptr(sums), ptr(n_valid), int(pixels_global),
+              float(ce_weight), float(reg_weight), ptr(terms), _stream())

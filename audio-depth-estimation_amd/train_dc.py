@@ -424,3 +424,120 @@ def main_base_residual(argv=None):
     step = lambda tr, b: tr.step(b[0], b[1])[0]
     return _run(args, cfg, model, trainer, 'audio', step, lambda m, b: m(b[0])[2], args.experiment_name,
                 ckpt_fmt='checkpoint_{}.pth', on_epoch=on_epoch, dist_info=di)
+
+
+# ---- train_coarse_depth.py ---------------------------------------------------------------------------------------------------
+def warm_restart_lr(epoch, base_lr, T_0=20, T_mult=2, eta_min=1e-6):
+    """Learning rate DURING epoch ``epoch`` (0-based) of torch's CosineAnnealingWarmRestarts stepped once per epoch."""
+    T_i, T_cur = T_0, epoch
+    while T_cur >= T_i:
+        T_cur -= T_i
+        T_i *= T_mult
+    return eta_min + (base_lr - eta_min) * (1 + math.cos(math.pi * T_cur / T_i)) / 2
+
+
+def main_coarse(argv=None):
+    """/root/reference/train_coarse_depth.py:133-645 for model_type 'unet': CoarseDepthUNet, CoarseDepthLoss (soft CE, or
+    focal with --use_focal) with valid = depth > 0, AdamW(wd 0.01) / Adam / SGD(momentum 0.9), clip_grad_norm_(1.0),
+    CosineAnnealingWarmRestarts(20, 2, 1e-6) per epoch; checkpoints ./checkpoints/<experiment>/checkpoint_N.pth and
+    best.pth with {epoch, state_dict, optimizer, bin_centers, bin_edges}.  Targets are binned on the device."""
+    from .coarse_engine import CoarseDepthTrainer
+    from .dataloader.utils_dataset import compute_bins
+    from .models.coarse_depth_model import CoarseDepthLoss, define_coarse_depth_model
+    p = argparse.ArgumentParser(description='Train Coarse Depth Classification Model (MI355X)')
+    p.add_argument('--dataset', type=str, default='batvisionv2', choices=['batvisionv1', 'batvisionv2'])
+    p.add_argument('--sparse_method', type=str, default='downup_015')
+    p.add_argument('--n_bins', type=int, default=128)
+    p.add_argument('--bin_mode', type=str, default='linear', choices=['linear', 'log', 'sid'])
+    p.add_argument('--sid_alpha', type=float, default=0.6)
+    p.add_argument('--model_type', type=str, default='unet', choices=['unet', 'lite', 'hybrid', 'dual_reg'])
+    p.add_argument('--base_channels', type=int, default=64)
+    p.add_argument('--offset_reg_weight', type=float, default=0.01)
+    p.add_argument('--coarse_weight', type=float, default=1.0)
+    p.add_argument('--final_weight', type=float, default=1.0)
+    p.add_argument('--batch_size', type=int, default=16)
+    p.add_argument('--learning_rate', type=float, default=0.001)
+    p.add_argument('--epochs', type=int, default=100)
+    p.add_argument('--optimizer', type=str, default='AdamW', choices=['Adam', 'AdamW', 'SGD'])
+    p.add_argument('--ce_weight', type=float, default=1.0)
+    p.add_argument('--regression_weight', type=float, default=0.5)
+    p.add_argument('--use_focal', action='store_true')
+    p.add_argument('--soft_ce_sigma', type=float, default=2.0)
+    p.add_argument('--validation', type=lambda x: str(x).lower() == 'true', default=True)
+    p.add_argument('--validation_iter', type=int, default=2)
+    p.add_argument('--experiment_name', type=str, default='exp1')
+    p.add_argument('--checkpoints', type=int, default=None)
+    p.add_argument('--use_wandb', action='store_true', default=False)
+    p.add_argument('--wandb_project', type=str, default='batvision-depth-estimation')
+    p.add_argument('--wandb_entity', type=str, default='branden')
+    g = p.add_argument_group('MI355X')
+    g.add_argument('--precision', type=str, default='bf16', choices=['bf16', 'f32'])
+    g.add_argument('--graph', action='store_true', help='replay the step as one hipGraph')
+    g.add_argument('--synthetic', type=int, default=0, help='train on N BatVision-shaped random items')
+    args = p.parse_args(argv)
+    cfg = load_config(dataset_name=args.dataset, mode='train', experiment_name=args.experiment_name)
+    exp = f'coarse_{args.sparse_method}_{args.bin_mode}{args.n_bins}_{args.model_type}_{args.experiment_name}'
+    if not args.synthetic:
+        raise NotImplementedError('the sparse-depth dataset needs file decoding that is not available in this build '
+                                  '(preprocessed .npy depth maps + audio files); use --synthetic N')
+    S, md = cfg.dataset.images_size, cfg.dataset.max_depth
+    rank, world, local, reducer = di = _dist()
+    args.device, args.num_workers, args.seed = 'cuda', 0, 42
+    dev = _device(args, local if world > 1 else None)
+    say = print if rank == 0 else (lambda *a, **k: None)
+    model = define_coarse_depth_model(model_type=args.model_type, input_channels=2, n_bins=args.n_bins,
+                                      base_channels=args.base_channels, output_size=S)
+    edges, centers = compute_bins(args.n_bins, args.bin_mode, None, md, args.sid_alpha)
+    norm = md if cfg.dataset.depth_norm else 1.0
+    model.compute_dtype = PRECISIONS[args.precision]
+    model = model.to(dev).train()
+    model.set_bin_centers((centers / norm).to(dev))
+    dev_edges = (edges / norm).to(dev)
+    say(f'Experiment: {exp}\nParameters: {model.get_num_params():,}')
+    criterion = CoarseDepthLoss(n_bins=args.n_bins, ce_weight=args.ce_weight, regression_weight=args.regression_weight,
+                                use_focal=args.use_focal, use_soft_ce=not args.use_focal, soft_ce_sigma=args.soft_ce_sigma)
+    eng = model.engine()
+    trainer = CoarseDepthTrainer.from_criterion(eng, criterion, optimizer=args.optimizer, lr=args.learning_rate,
+                                                weight_decay=0.01 if args.optimizer == 'AdamW' else 0.0, clip_norm=1.0,
+                                                ddp=reducer)
+    if args.graph:
+        trainer.enable_graph(after_steps=3)
+    tl, vl, sampler, fe = _loaders(cfg, args, 'audio', rank, world)
+    ckpt_dir = os.path.join('./checkpoints', exp)
+    os.makedirs(ckpt_dir, exist_ok=True)
+    start, ck = 1, None
+    if args.checkpoints is not None:
+        ck = torch.load(os.path.join(ckpt_dir, f'checkpoint_{args.checkpoints}.pth'), map_location=dev)
+        model.load_state_dict({k[7:] if k.startswith('module.') else k: v for k, v in ck['state_dict'].items()})
+        start = ck['epoch'] + 1
+        say(f'Resumed from epoch {args.checkpoints}')
+    if not eng._bound():
+        eng.bind_parameters()
+    if reducer is not None:
+        reducer.broadcast_parameters(eng.flat_p)
+    if ck is not None and isinstance(ck.get('optimizer'), dict):
+        trainer.load_state_dict(ck['optimizer'], dev)
+    best = float('inf')
+    for epoch in range(start, args.epochs + 1):
+        trainer.lr = warm_restart_lr(epoch - 1, args.learning_rate)
+        if sampler is not None:
+            sampler.set_epoch(epoch)
+        t0, acc = time.time(), []
+        for batch in tl:
+            audio, gt = _to_device(batch, dev, fe)
+            _, terms = trainer.step(audio, None, gt / norm, edges=dev_edges)
+            acc.append(terms.detach().clone())
+        m = torch.stack(acc).mean(0).tolist() if acc else [float('nan')] * 3
+        say(f'Epoch {epoch}: total={m[2]:.4f}, ce={m[0]:.4f}, reg={m[1]:.4f}, time={time.time() - t0:.1f}s')
+        state = {'epoch': epoch, 'state_dict': model.state_dict(), 'optimizer': trainer.state_dict(),
+                 'bin_centers': centers, 'bin_edges': edges}
+        if args.validation and epoch % args.validation_iter == 0:
+            errs = _validate(model, vl, dev, lambda mm, b: mm.engine().forward_net(b[0], False)[1] * norm, fe)
+            say(f'Val - RMSE: {errs["rmse"]:.3f}, ABS_REL: {errs["abs_rel"]:.3f}, Delta1: {errs["delta1"]:.3f}')
+            if errs['rmse'] < best:
+                best = errs['rmse']
+                if rank == 0:
+                    torch.save(dict(state, val_rmse=best), os.path.join(ckpt_dir, 'best.pth'))
+        if epoch % cfg.mode.saving_checkpoints == 0 and rank == 0:
+            torch.save(state, os.path.join(ckpt_dir, f'checkpoint_{epoch}.pth'))
+    return model

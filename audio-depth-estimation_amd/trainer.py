@@ -83,6 +83,7 @@ class OptimTail(GraphedStep):
     OPT = {'AdamW': 0, 'Adam': 1, 'SGD': 2}
     _ready = False
     _flat_id = None
+    _captured_hyper = None
     _optim_offset = 0           # the optimised range is [offset:] of every flat buffer
 
     def _init_optim(self, engine, optimizer, lr, betas, eps, weight_decay, clip_norm, ddp):
@@ -101,6 +102,23 @@ class OptimTail(GraphedStep):
         if self.ddp is not None:
             raise RuntimeError('graph capture of the step is only wired for single-process training')
         super().enable_graph(after_steps)
+
+    def _hyper(self):
+        """What adn_grad_norm / adn_optimizer_step take BY VALUE: a captured step has these frozen inside it."""
+        return (self.lr, tuple(self.betas), self.eps, self.weight_decay, self.clip_norm)
+
+    def _graphed(self, *inputs):
+        """A hipGraph / launch plan replays the optimizer's by-value arguments of the step it was captured from, so a
+        captured step whose hyper-parameters changed since (a per-epoch learning-rate schedule: ``trainer.lr = ...``) is
+        dropped here and captured again by this very call, with the new values."""
+        captured = self._graph is not None or self._plan is not None
+        if captured and self._hyper() != self._captured_hyper:
+            self._graph = self._plan = None
+            captured = False
+        out = super()._graphed(*inputs)
+        if not captured and (self._graph is not None or self._plan is not None):
+            self._captured_hyper = self._hyper()
+        return out
 
     def _optim_meta(self):
         """(param, offset, numel) of the parameters the reference's optimizer holds, in its order."""

@@ -642,6 +642,47 @@ int adn_vae_bwd(const void* g_rec, int32_t dtype, int32_t B, int32_t C, int32_t 
                 float* dw_dec, float* db_dec, const float* kl, float* loss, void* dh, void* workspace,
                 int64_t workspace_bytes, void* stream);
 
+/* Coarse-depth classification family (models/coarse_depth_model.py, train_coarse_depth.py:446-463): the loss head behind
+ * the 1x1 class conv.  f32 arithmetic, f64 final reductions, no atomics, bit-reproducible.
+ *
+ * adn_coarse_targets: BinnedDepthDataset.depth_to_bins on the device.  depth f32 [n]; edges = the nb - 1 INTERIOR bin
+ * edges (bin_edges[1:-1]); bins int32 [n] = clamp(torch.bucketize(depth, edges, right=False), 0, nb - 1) with exact f32
+ * compares (NaN sorts behind every edge, as in torch: bin nb - 1); stats[0] (f64) = number of depth > 0.  bins == NULL: the count alone (edges / nb unused).
+ * workspace: adn_coarse_targets_workspace_bytes(n). */
+int64_t adn_coarse_targets_workspace_bytes(int64_t n);
+int adn_coarse_targets(const float* depth, int64_t n, const float* edges, int32_t nb, int32_t* bins, double* stats,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+/* adn_coarse_loss: ONE pass over the class logits [pixels][ld] (dtype, nb <= ld, 2 <= nb <= 512).  Per pixel:
+ * depth = sum_k softmax_k centers[k] (CoarseDepthUNet.forward :163-166), optionally argmax (first maximum, predict_depth
+ * mode 'hard').  With bins (needs gt, n_valid = device f64[1] GLOBAL valid count, workspace): the per-pixel
+ * classification loss (ce_mode 0: SoftCrossEntropyLoss(sigma) :335-355, labels exp(-((k-t)/sigma)^2/2) / (sum + 1e-8);
+ * 1: FocalLoss(gamma) :368-384; 2: nn.CrossEntropyLoss) and |depth - gt| on gt > 0 go into per-block f64 partials in the
+ * workspace.  With dlogits ([pixels][ld], dtype): the gradient of
+ * ce_weight * mean_over_pixels_global(ce) + reg_weight * sum_valid |depth - gt| / n_valid, columns [nb, ld) = 0
+ * (n_valid == 0: the classification part alone, as autograd leaves it). */
+typedef struct {
+  const void* logits;
+  int32_t dtype, nb, ld, ce_mode;
+  int64_t pixels, pixels_global;     /* pixels_global: pixel count of the global batch under data parallelism */
+  const float* centers;              /* [nb] */
+  const int32_t* bins;               /* [pixels] or NULL (forward only) */
+  const float* gt;                   /* [pixels] */
+  const double* n_valid;
+  float sigma, gamma, ce_weight, reg_weight;
+  float* depth;                      /* [pixels] */
+  int32_t* argmax;                   /* [pixels] or NULL */
+  void* dlogits;                     /* or NULL */
+  void* workspace;
+  int64_t workspace_bytes;
+} AdnCoarseLoss;
+int64_t adn_coarse_loss_workspace_bytes(int64_t pixels);
+int adn_coarse_loss(const AdnCoarseLoss* d, void* stream);
+/* workspace != NULL: reduce the partials adn_coarse_loss left for `pixels` pixels into sums f64[2] = (sum ce, sum masked
+ * |depth - gt|); NULL: take sums as given (all-reduced by the caller).  terms != NULL: terms f32[3] = (ce = sums[0] /
+ * pixels_global, regression = sums[1] / n_valid (NaN when n_valid == 0), total = ce_weight ce + reg_weight regression). */
+int adn_coarse_loss_finish(const void* workspace, int64_t pixels, double* sums, const double* n_valid,
+                           int64_t pixels_global, float ce_weight, float reg_weight, float* terms, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
