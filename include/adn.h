@@ -83,7 +83,7 @@ typedef struct {
 
 typedef struct {
   int32_t dtype;      /* ADN_F32 / ADN_BF16: dtype of activations and packed weights             */
-  int32_t geom;       /* ADN_GEMM_S2 / ADN_GEMM_T2                                               */
+  int32_t geom;       /* ADN_GEMM_S2 / ADN_GEMM_T2 / ADN_GEMM_S1 (with ks)                       */
   int32_t B;          /* batch                                                                   */
   int32_t Hs, Ws;     /* SMALL grid (S2: output; T2: input)                                      */
   int32_t C0, C1;     /* channels of the two gathered input sources (virtual concat), C1 may be 0*/

@@ -5,11 +5,17 @@ Every call goes through the C ABI (ctypes -> libadn.so).  Tolerances (stated per
   * bf16 path: inputs are pre-rounded to bf16 and the reference is computed in fp32 from the SAME
     rounded values, so only accumulation order and the final store rounding differ:
     f32 outputs <= 1e-4 * max|ref|, bf16 outputs <= 6e-3 * max|ref| (one bf16 ulp = 2^-8 relative).
+
+The implicit-GEMM tests of this module launch the RAW, Z_STATS and BWD epilogues.  The other three -- ACT, FINAL and ADD --
+are covered in tests/test_gpu_igemm_epilogues.py, on every kernel form that can carry them and against a float64
+reference; its shapes live in tests/igemm_epilogue_cases.py and are part of igemm_launches() / IGEMM_FORMS below.
 """
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+import igemm_epilogue_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -623,11 +629,13 @@ IGEMM_FORMS = {
     'patch_stats1/S2/64x8x16_64+0_512': 'patch 128x64', 'patch_stats3/S2/64x8x16_64+0_512': 'patch 128x64',
     'patch_stats1/T2/16x8x16_64+0_256': 'patch 128x64', 'patch_stats3/T2/16x8x16_64+0_256': 'patch 128x64',
 }
+# ... and the S2 / T2 launches of tests/test_gpu_igemm_epilogues.py (ACT, FINAL, ADD), forms as its case table names them
+IGEMM_FORMS.update({r['name'][:-5]: r['form'] for r in igemm_epilogue_cases.launch_rows(s1=False) if r['dtype'] == 1})
 
 
 def igemm_launches():
-    """Every adn_igemm launch of the igemm tests of this module as the planner sees it (rows in the form of
-    tools/igemm_plan_table.py; the name is `test/geometry/shape/dtype`).  Host only."""
+    """Every adn_igemm launch of the igemm tests of this module, and the S2 / T2 launches of test_gpu_igemm_epilogues.py, as
+    the planner sees them (rows in the form of tools/igemm_plan_table.py; the name is `test/geometry/shape/dtype`).  Host only."""
     rows = []
 
     def add(test, dt, geom, B, Hs, C0, C1, N, epi, segs=None, Ws=None):
@@ -654,6 +662,7 @@ def igemm_launches():
     for geom, B, C0, N in PATCH_STATS_CASES:
         for epi in (1, 3):
             add('patch_stats%d' % epi, 1, geom, B, PATCH_HS, C0, 0, N, epi, Ws=PATCH_WS)
+    rows += [{k: v for k, v in r.items() if k != 'form'} for r in igemm_epilogue_cases.launch_rows(s1=False)]
     return rows
 
 

@@ -279,12 +279,62 @@ def test_igemm_gpu_test_shapes_reach_the_forms_they_name():
     assert epis('patch 128x128', (0,)) >= {0}
     for form in ('patch-tall 256x64', 'patch-pair 128x128'):     # T2 only (the S2 pair form lost to split-K, tall needs T2 / S1)
         assert epis(form, (1,)) >= {0, 1, 3}, form
+    # ACT (2) is the eval-mode forward of the same layers: every non-ring form must carry it too; FINAL (4) and ADD (5) must
+    # reach the direct path, a split tile (both: the scalar epilogue), an unsplit tile and a patch form (the vector epilogue)
+    for form in ('tile 128x128', 'tile 128x64', 'tile 256x64', 'tile 256x128', 'tile 128x128 split', 'tile 128x64 split', 'direct'):
+        assert 2 in epis(form), form
+    for geom in (0, 1):
+        assert 2 in epis('patch 128x64', (geom,)), geom
+    assert 2 in epis('patch 128x128', (0,))
+    for form in ('patch-tall 256x64', 'patch-pair 128x128'):
+        assert 2 in epis(form, (1,)), form
+    by_epi = lambda epi: {form for (form, _), e in reached.items() if epi in e}
+    for epi in (4, 5):
+        forms = by_epi(epi)
+        assert 'direct' in forms, epi
+        assert any(f.startswith('tile') and f.endswith('split') for f in forms), epi
+        assert any(f.startswith('tile') and not f.endswith('split') for f in forms), epi
+        assert any(f.startswith('patch') for f in forms), epi
     # the patch kernel's stats epilogues run off the ring kernel's 16 x 16 grid, at the smallest B that plans unsplit
     for geom, B, C0, N in tg.PATCH_STATS_CASES:
         for b, want in ((B, 'patch'), (B - 1, 'tile')):
             r = dict(name='', dtype=1, geom=geom, B=b, Hs=tg.PATCH_HS, Ws=tg.PATCH_WS, C0=C0, C1=0, N=N, epi=1, segs=[N], ks=0)
             p = tool.query_row(r)['plan']
             assert p.split()[0] == want and ('nsplit=1 ' in p) == (b == B), p
+
+
+def test_igemm_epilogue_s1_shapes_reach_the_forms_they_name():
+    """The stride-1 launches of tests/test_gpu_igemm_epilogues.py (ACT and ADD; FINAL has no stride-1 user) run the kernel
+    form their case table names, and every case of that module -- S2 / T2 ones included, which the test above and the plan
+    table pin -- names a shape whose form the planner confirms.  ACT reaches every stride-1 form, ADD the unsplit 1 x 1
+    tiles of the attention block, a 3 x 3 patch form, a split tile and the direct path."""
+    import igemm_epilogue_cases as ec
+    tool = _igemm_plan_tool()
+    rows = ec.launch_rows(s1=True)
+    assert len(rows) >= 20 and all(r['geom'] == 2 for r in rows)
+    for r in rows + ec.launch_rows(s1=False):
+        assert ec.plan_form(tool.query_row(r)['plan']) == r['form'], r['name']
+    for epi, key_cases in ec.CASES.items():                       # the variant of every case exists and fits its shape
+        for key, var in key_cases:
+            sets = {ec.ACT: ec.ACT_VARIANTS, ec.ADD: ec.ADD_VARIANTS}.get(epi, {var: [None]})[var]
+            assert len(sets) in (1, len(ec.SHAPES[key]['segs'])), (key, var)
+            assert max(ec.SHAPES[key][d] for d in ('B', 'Hs', 'Ws')) <= 256
+            assert ec.SHAPES[key]['B'] * ec.SHAPES[key]['Hs'] * ec.SHAPES[key]['Ws'] <= 16 * 64 * 64, key
+    forms = lambda epi, ks: {r['form'] for r in rows if r['epi'] == epi and r['ks'] == ks}
+    assert forms(ec.ACT, 3) >= {'direct', 'tile 128x128 split', 'tile 128x64', 'patch 128x64', 'patch 128x128', 'patch-tall 256x64'}
+    assert forms(ec.ACT, 1) >= {'tile 128x64', 'tile 256x64', 'tile 128x128'}
+    assert forms(ec.ADD, 1) >= {'tile 128x128', 'tile 128x64', 'tile 256x64'}
+    assert forms(ec.ADD, 3) >= {'direct', 'tile 128x128 split', 'patch 128x64'}
+    assert not forms(ec.FINAL, 1) and not forms(ec.FINAL, 3)
+    # what the mutation checks of the module rely on: the gate, a two-segment slope pair, an out0-only launch, ACT with
+    # shift and bias, and FINAL's identity each run behind the scalar epilogue AND the vector one
+    scalar = lambda key: ec.SHAPES[key]['form'] == 'direct' or ec.SHAPES[key]['form'].endswith('split')
+    for epi, pick in ((ec.ADD, lambda v: v in ('gate', 'gate_chan')), (ec.ACT, lambda v: v == 'slopes'),
+                      (ec.ACT, lambda v: v in ('scale', 'qkv')), (ec.ACT, lambda v: v == 'full'),
+                      (ec.FINAL, lambda v: v[0] == 2)):
+        for dt in (ec.F32, ec.BF16):
+            paths = {scalar(key) for key, var in ec.CASES[epi] if pick(var) and ec.SHAPES[key]['dtype'] == dt}
+            assert paths == {False, True}, (epi, dt)
 
 
 def test_launch_plan_capture_and_replay_state_machine():

@@ -30,8 +30,10 @@ def row(name, dtype, geom, B, Hs, C0, C1, N, epi=RAW, segs=None, ks=0, Ws=None):
 
 
 def gpu_test_shapes():
-    """The launches of the igemm tests of tests/test_gpu_kernels.py (igemm_launches() there builds them)."""
+    """The launches of the igemm tests of tests/test_gpu_kernels.py and tests/test_gpu_igemm_epilogues.py
+    (igemm_launches() of the former builds them)."""
     import importlib.util
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))          # (the module imports its case tables from beside it)
     spec = importlib.util.spec_from_file_location('test_gpu_kernels', os.path.join(ROOT, 'tests', 'test_gpu_kernels.py'))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
