@@ -806,9 +806,21 @@ def pool_workspace_bytes(B, HW, Cc, nq=1):
     return _lib.load().adn_pool_workspace_bytes(B, HW, Cc, nq)
 
 
+def _contiguous(who, **named):
+    """The AdaBins kernels index by shape alone: a strided view would be read (or written) at the wrong addresses."""
+    for name, t in named.items():
+        if t is not None and not t.is_contiguous():
+            raise RuntimeError(f'{who}: {name} must be contiguous, got shape {tuple(t.shape)} with strides {tuple(t.stride())}')
+
+
 def pool(x, y, B, HW, Cc, nq, scale, out, workspace):
-    """x (and y) [B,HW,Cc] NHWC views -> out f32 [B,Cc] (nq=1: scale*sum x) or [B,3,Cc] (sum x^2, y^2, x*y)."""
+    """x (and y) [B,HW,ld] contiguous NHWC tensors, ld = x.shape[-1] >= Cc (the first Cc channels of every row are
+    summed) -> out f32 [B,Cc] (nq=1: scale*sum x) or [B,3,Cc] (sum x^2, y^2, x*y).  A channel-sliced view such as
+    buf[..., :Cc] is refused: pass buf itself."""
     _dev(x, y, out, workspace)
+    _contiguous('pool', x=x, y=y, out=out)
+    if x.numel() != B * HW * x.shape[-1] or (y is not None and (y.shape != x.shape or y.dtype != x.dtype)):
+        raise RuntimeError(f'pool: x has shape {tuple(x.shape)} for B={B}, HW={HW} (y: {None if y is None else tuple(y.shape)})')
     _lib.call('adn_pool', ptr(x), ptr(y), B, HW, Cc, x.shape[-1], nq, dtype_code(x.dtype), float(scale), ptr(out),
               ptr(workspace), _nbytes(workspace), _stream())
 
@@ -894,6 +906,7 @@ def vae_bwd(g_rec, h, mu, logvar, eps, z, w_mu, w_lv, w_dec, g_kl, dw_mu, db_mu,
 def bcast_add(gx, dg, scale, accumulate):
     B, H, W, Cc = gx.shape
     _dev(gx, dg)
+    _contiguous('bcast_add', gx=gx, dg=dg)
     _lib.call('adn_bcast_add', ptr(gx), ptr(dg), B, H * W, Cc, float(scale), int(bool(accumulate)), dtype_code(gx.dtype),
               _stream())
 
@@ -901,6 +914,7 @@ def bcast_add(gx, dg, scale, accumulate):
 def bins_fwd(logits, centers, base):
     B, H, W, nb = logits.shape
     _dev(logits, centers, base)
+    _contiguous('bins_fwd', logits=logits, centers=centers, base=base)
     _lib.call('adn_bins_fwd', ptr(logits), ptr(centers), B, H * W, nb, dtype_code(logits.dtype), ptr(base), _stream())
 
 
@@ -911,6 +925,7 @@ def bins_bwd_workspace_bytes(B, HW, nb):
 def bins_bwd(logits, centers, base, dbase, dmean, dlogits, dcent, workspace):
     B, H, W, nb = logits.shape
     _dev(logits, centers, base, dbase, dmean, dlogits, dcent, workspace)
+    _contiguous('bins_bwd', logits=logits, centers=centers, base=base, dbase=dbase, dmean=dmean, dlogits=dlogits, dcent=dcent)
     _lib.call('adn_bins_bwd', ptr(logits), ptr(centers), ptr(base), ptr(dbase), ptr(dmean), B, H * W, nb,
               dtype_code(logits.dtype), ptr(dlogits), ptr(dcent), 0, ptr(workspace), _nbytes(workspace), _stream())
 
@@ -930,6 +945,7 @@ def distill_pix_grad(base, resid, gt, teacher, max_depth, stats, lt, lr, ls, dba
 def featcos_grad(a, r, stats, coef, ga):
     B, H, W, Cc = a.shape
     _dev(a, r, stats, ga)
+    _contiguous('featcos_grad', a=a, r=r, stats=stats, ga=ga)
     _lib.call('adn_featcos_grad', ptr(a), ptr(r), ptr(stats), B, H * W, Cc, dtype_code(a.dtype), float(coef), ptr(ga),
               _stream())
 

@@ -209,7 +209,9 @@ def adabins_branch(sd, enc, pred, dec, x, max_depth, training, new_stats, drop_m
             prev = sd[k]
             batch = (once - (1 - BN_MOMENTUM) * prev) / BN_MOMENTUM
             new_stats[k] = (1 - BN_MOMENTUM) * once + BN_MOMENTUM * batch
-    logits = F.conv2d(d, sd[dec + '.class_head.weight'], sd[dec + '.class_head.bias'])
+    # the engine's class head is an MFMA GEMM over the compute-dtype weight copy, and its logits stay in the compute dtype
+    # (soft binning, their spatial mean and the backward all read that stored copy); the 1x1 depth heads run in f32
+    logits = _q(F.conv2d(d, _q(sd[dec + '.class_head.weight']), sd[dec + '.class_head.bias']))
     resid_raw = F.conv2d(d, sd['residual_head.weight'], sd['residual_head.bias'])
     if output_size is not None and logits.shape[-1] != output_size:           # :196-198, :334-337, :383-386
         logits = F.interpolate(logits, size=(output_size, output_size), mode='nearest')

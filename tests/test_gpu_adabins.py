@@ -2,7 +2,11 @@
 
   * csrc/adabins.hip kernels against torch-CPU fp32 references of the reference's formulas
     (adabins_distillation_model.py:127-149, 198-201; utils_distillation_loss.py:48-143): <= 2e-5 of max|ref| (f32),
-    bf16-stored tensors <= 6e-3;
+    bf16-stored tensors <= 6e-3 -- one shape per kernel here; every branch the host code can dispatch (pool parts, the
+    scalar / vector row sums, the three soft-binning kernels, grid-stride loops, the predictor's limits, the loss
+    kernels past one block and with no valid pixel) is walked in tests/test_gpu_adabins_kernels.py against float64;
+  * the bf16 engine (the default compute dtype) against the float64 oracle with bf16 storage emulated
+    (test_adabins_bf16_against_oracle);
   * the whole model + fused distillation step against the golden vectors produced by the REFERENCE at its only
     valid width (base_channels 64, tests/golden/adabins32_bc64.npz): f32 compute; forward outputs <= 2e-4, loss terms
     <= 2e-4, per-parameter gradient norm <= 5e-3 and sampled gradient entries <= 5e-3 of the tensor max, decoder
@@ -531,3 +535,89 @@ def test_fused_step_and_autograd_loop_agree_for_a_fractional_resize():
             continue
         gb = mb.engine().grad_view(q)
         assert float((p.grad - gb).abs().max()) <= 2e-5 * float(gb.abs().max()) + 1e-12, k
+
+
+def test_adabins_bf16_against_oracle():
+    """base_channels 64 at 64x64, B = 2, compute dtype bf16 (what training runs by default), dropout p = 0, frozen teacher:
+    one fused distillation step against the float64 oracle with bf16 rounding at the engine's storage points
+    (dcnet_oracle.QUANT: conv operands, stored z, stored activations, the class head's weight copy and its stored logits)
+    + distillation_loss + backward().  Bounds of test_rgb_full_width_against_oracle for the same encoder / decoder stack:
+    maps, vectors, loss terms and BatchNorm running statistics <= 3e-2 (relative L1 / relative) -- measured: residual
+    8.9e-3 (teacher 1.0e-2), running statistics 3.8e-3, final depth 1.7e-3, mean logits 2.4e-3, every loss term <= 5.4e-4.
+    Per-parameter gradient cosine: measured 0.893 (audio_encoder.inc.double_conv.1.bias) .. 1.0, median 0.947, one tensor
+    of 61 under 0.9 -- so the bound is the binaural test's 0.6, not 0.9.  Reason: unlike the RGB test, which feeds both
+    sides the ORACLE's d loss / d pred, the fused step differentiates its own bf16 prediction, and the L1 and |residual|
+    terms have sign() gradients: sign(residual) differs from the oracle's on 0.45 % of the pixels.  With the oracle's loss
+    gradients fed to backward_student instead, the same tensors measure 0.9195 .. 1.0 (none under 0.9); the rest is the
+    ~1.7x per conv amplification of bf16 rounding described in test_gpu_dcnet.py."""
+    from audio_depth_estimation_amd.adabins_engine import AdaBinsTrainer
+    from audio_depth_estimation_amd.models.adabins_distillation_model import AdaBinsDistillationModel
+    from oracle import dcnet_oracle
+    torch.manual_seed(0)
+    S, maxd = 64, 30.0
+    lam, temp = (1.0, 0.5, 0.3, 0.2, 0.1), 4.0
+    model = AdaBinsDistillationModel(128, 64, S, maxd)
+    for mod in model.modules():
+        if isinstance(mod, torch.nn.Dropout):
+            mod.p = 0.0
+    model.compute_dtype = torch.bfloat16
+    model.freeze_rgb()
+    sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+    pkeys = [k for k, p in model.named_parameters() if p.requires_grad]
+    g = torch.Generator().manual_seed(1234)
+    audio, rgb = torch.rand(2, 2, S, S, generator=g), torch.rand(2, 3, S, S, generator=g)
+    gt = 30 * torch.rand(2, 1, S, S, generator=g)
+    gt[gt < 3] = 0
+    torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
+    sd64 = {k: (v.double() if v.is_floating_point() else v.clone()) for k, v in sd.items()}
+    for k in pkeys:
+        sd64[k].requires_grad_(True)
+    dcnet_oracle.QUANT = lambda t: t.float().bfloat16().to(t.dtype)
+    try:
+        ref, stats_ref = dcnet_oracle.adabins_forward(sd64, audio.double(), rgb.double(), maxd, training=True)
+        total_ref, parts = dcnet_oracle.distillation_loss(ref, gt.double(), gt > 0, *lam, temp)
+        total_ref.backward()
+    finally:
+        dcnet_oracle.QUANT = None
+
+    model = model.to(DEV).train()
+    eng = model.engine()
+    tr = AdaBinsTrainer(eng, *lam, temp, optimizer='AdamW', lr=1e-4, clip_norm=1.0)
+    total, terms = tr.step(audio.to(DEV), rgb.to(DEV), gt.to(DEV))
+    rel_l1 = lambda a, b: float((a.detach().double().cpu().reshape(b.shape) - b.detach()).abs().sum() / b.detach().abs().sum())
+    fig = {}
+    for side in ('audio', 'rgb'):
+        br, o = eng.branches[side], ref[side]
+        got = {'final_depth': br.final, 'base_depth': br.base, 'residual': br.head.result, 'bin_centers': br.centers,
+               'mean_logits': br.mean_logits}
+        want = dict(o, mean_logits=o['bin_logits'].mean((2, 3)))
+        for k, v in got.items():
+            fig[f'{side}/{k}'] = rel_l1(v, want[k])
+    names = ('task', 'response', 'feature', 'bin', 'bin_centers', 'sparse')
+    tv = terms.detach().double().cpu()
+    for i, k in enumerate(names):
+        fig['loss/' + k] = abs(float(tv[i]) - float(parts[k].detach())) / abs(float(parts[k].detach()))
+    fig['loss/total'] = abs(float(total) - float(total_ref.detach())) / abs(float(total_ref.detach()))
+    sd1 = model.state_dict()
+    worst = 0.0
+    for k, v in stats_ref.items():
+        v = v.detach()
+        worst = max(worst, float((sd1[k].double().cpu() - v).abs().max() / (v.abs().max() + 1e-30)))
+    fig['running_stats'] = worst
+    named = dict(model.named_parameters())
+    cosines = {}
+    for k in pkeys:
+        got = eng.grad_view(named[k]).detach().double().cpu().reshape(-1)
+        want = sd64[k].grad.reshape(-1)
+        if got.numel() > 1:
+            cosines[k] = float(torch.dot(got, want) / (got.norm() * want.norm() + 1e-300))
+        else:
+            assert bool(torch.isfinite(got).all()), k
+    lo = min(cosines, key=cosines.get)
+    print('adabins bf16 vs oracle:', {k: f'{v:.3e}' for k, v in fig.items()}, 'min gradient cosine', lo, cosines[lo])
+    print('gradient cosines below 0.95:', {k: round(v, 4) for k, v in cosines.items() if v < 0.95})
+    for k, v in fig.items():
+        assert v <= 3e-2, (k, v)
+    for k, v in cosines.items():
+        assert v >= 0.6, (k, v)
+
