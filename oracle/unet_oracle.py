@@ -84,8 +84,12 @@ def _bn(x, sd, key, training, new_stats):
 
 
 def unet_forward(sd: dict, x: torch.Tensor, num_downs: int, depth_norm: bool,
-                 training: bool = True):
+                 training: bool = True, pre_acts: list | None = None):
     """Forward of define_G(...)'s module.  Returns (out, new_running_stats).
+
+    ``pre_acts``: when a list, every tensor a ReLU / LeakyReLU decides on (the output of each
+    down and up conv after its norm) is appended to it, detached: a test can then see how far
+    from a kink of the network its reference was taken.
 
     ``sd`` maps reference key names to tensors (leaf tensors with requires_grad for a
     backward through torch autograd).  Follows the Sequential order of
@@ -101,6 +105,8 @@ def unet_forward(sd: dict, x: torch.Tensor, num_downs: int, depth_norm: bool,
         h = F.conv2d(a, sd[k['down'] + '.weight'], None, stride=2, padding=1)   # :187
         if k['bn_d'] is not None:
             h = _bn(h, sd, k['bn_d'], training, new_stats)            # downnorm :190
+        if pre_acts is not None:
+            pre_acts.append(h.detach())
     # h = output of the innermost down conv (no norm)
     u = None
     for i in reversed(range(num_downs)):
@@ -111,6 +117,8 @@ def unet_forward(sd: dict, x: torch.Tensor, num_downs: int, depth_norm: bool,
         u = F.conv_transpose2d(a, sd[k['up'] + '.weight'], bias, stride=2, padding=1)
         if k['bn_u'] is not None:
             u = _bn(u, sd, k['bn_u'], training, new_stats)            # upnorm :192
+        if pre_acts is not None:
+            pre_acts.append(u.detach())
     out = torch.sigmoid(u) if depth_norm else F.relu(u)               # :201-206
     return out, new_stats
 

@@ -10,6 +10,7 @@
     gradient cosine >= 0.93 per tensor at B=2 (BatchNorm over 8 values at the bottleneck amplifies bf16
     rounding; see DESIGN.md for the measured values at larger batch).
 """
+import functools
 import os
 from types import SimpleNamespace
 
@@ -110,7 +111,7 @@ def test_golden_reference_parity_f32(name, netG):
             assert float((sd2[k].cpu() - ref).abs().max()) <= 0.02 * lr, k
 
 
-def _oracle_step(sd, audio, gt, nd, depth_norm, hyper):
+def _oracle_step(sd, audio, gt, nd, depth_norm, hyper, pre_acts=None):
     from oracle import loss_oracle, unet_oracle
     l1w, sw, lam, max_depth = hyper
     sd = {k: (v.double() if v.is_floating_point() else v.clone()) for k, v in sd.items()}
@@ -118,7 +119,7 @@ def _oracle_step(sd, audio, gt, nd, depth_norm, hyper):
     pkeys = unet_oracle.param_keys(nd)
     for k in pkeys:
         sd[k].requires_grad_(True)
-    pred, stats = unet_oracle.unet_forward(sd, audio, nd, depth_norm, training=True)
+    pred, stats = unet_oracle.unet_forward(sd, audio, nd, depth_norm, training=True, pre_acts=pre_acts)
     loss = loss_oracle.masked_loss(pred, gt, 'Combined', l1w, sw, lam, scale=max_depth if depth_norm else 1.0)
     loss.backward()
     return pred.detach(), loss.item(), {k: sd[k].grad for k in pkeys}, stats
@@ -161,6 +162,104 @@ def test_full_width_unet256_against_oracle(dtype):
         got = model.state_dict()[k].cpu()
         v = v.float()
         assert float((got - v).abs().max()) <= (1e-5 if dtype == torch.float32 else 2e-2) * float(v.abs().max()) + 1e-6, k
+
+
+RECT_H, RECT_W = 128, 384            # 1:3: the small grids run 64 x 192 down to 1 x 3, none square, none a power of two
+RECT_HYPER = (0.237, 0.637, 0.869, 30.0)
+# The network is piecewise linear in its 6 M ReLU / LeakyReLU arguments, and its gradient jumps where one of them changes
+# sign: a reference gradient taken with an argument within f32 rounding of 0 says nothing about an f32 run.  With seed 4321
+# the float64 oracle has the up-BatchNorm output of level 3 (16 x 48) at 2.4e-7 in one element; taking that one decision the
+# other way IN float64 moves the weight gradients by 2.6e-4 (outermost down conv) ... 3.4e-2 (up conv of level 3) of the
+# tensor max, prediction and loss by < 1e-11.  So the input seed is the first one (counting from 1) whose oracle keeps every
+# such argument at least RECT_KINK_MARGIN of its tensor's RMS away from 0, which the test asserts on the oracle alone:
+# 1e-6 = 16 ulp of f32 at the tensors' RMS of 1, 7x the f32 run's prediction error (1.4e-7 relative L1).
+RECT_SEED = 39
+RECT_KINK_MARGIN = 1e-6
+
+
+def _rect_inputs():
+    g = torch.Generator().manual_seed(RECT_SEED)
+    audio = torch.rand(2, 2, RECT_H, RECT_W, generator=g)
+    gt = 30 * torch.rand(2, 1, RECT_H, RECT_W, generator=g)
+    gt[gt < 3] = 0
+    return audio, gt
+
+
+def _rect_state_dict():
+    """The seed-0 unet_128 / ngf 64 weights (CPU, f32) both dtypes start from."""
+    from audio_depth_estimation_amd.models.unetbaseline_model import define_G
+    torch.manual_seed(0)
+    model = define_G(_cfg(False), 2, 1, 64, 'unet_128')
+    with torch.no_grad():      # keep predictions away from 0 where SIlog's 1/pred is ill-conditioned
+        model.model.model[3].bias.fill_(1.0)
+    return {k: v.detach().clone() for k, v in model.state_dict().items()}
+
+
+@functools.lru_cache(maxsize=1)
+def _rect_oracle():
+    """One float64 oracle step and one eval-mode forward on the 128 x 384 input, shared by both dtypes; read-only.  The last
+    entry is the oracle's distance from a kink: min |argument| / RMS over every tensor a ReLU / LeakyReLU decides on."""
+    from oracle import unet_oracle
+    sd = _rect_state_dict()
+    audio, gt = _rect_inputs()
+    acts = []
+    pred, loss, grads, stats = _oracle_step(sd, audio, gt, 7, False, RECT_HYPER, pre_acts=acts)
+    kink = min(float(a.abs().min() / a.pow(2).mean().sqrt()) for a in acts)
+    with torch.no_grad():
+        sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+        pred_eval, _ = unet_oracle.unet_forward(sd64, audio.double(), 7, False, training=False)
+    return pred, loss, grads, stats, pred_eval, kink
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
+def test_rectangular_unet128_against_oracle(dtype):
+    """ngf=64 unet_128 on a 128 x 384 input, B=2: every level is rectangular and no power of two (64 x 192 ... 1 x 3), so the
+    4x4 stride-2 kernels decode pixels on their non-power-of-two branch, the weight gradients take other forms than on a
+    square image and the innermost level (1 x 3) runs the ordinary split tile kernel instead of the one-pixel form.  One
+    fused step against the float64 oracle at the bounds of the 256 x 256 test, the fused gradient norm against the norm of
+    the oracle's gradients (1e-4 f32, 2e-2 bf16), then the eval-mode prediction (the ACT epilogue on the same grids)."""
+    from audio_depth_estimation_amd.engine import FusedTrainer
+    f32 = dtype == torch.float32
+    pred_ref, loss_ref, grads_ref, stats_ref, pred_eval_ref, kink = _rect_oracle()
+    assert kink >= RECT_KINK_MARGIN, kink          # the reference itself: differentiable within f32 rounding of its forward
+    audio, gt = _rect_inputs()
+    model = _build('unet_128', 64, False, dtype, _rect_state_dict())
+    model.train()
+    tr = FusedTrainer(model.engine(), 'Combined', *RECT_HYPER[:3], max_depth=30.0, optimizer='AdamW', lr=0.002,
+                      clip_norm=1.0)
+    eng = model.engine()
+    p0 = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+    loss, pred = tr.step(audio.to(DEV), gt.to(DEV))
+    assert [(lv['hs'], lv['ws']) for lv in eng.levels] == [(64 >> i, 192 >> i) for i in range(7)]
+    print('%s: pred rel-L1 %.3e, loss rel %.3e' % (dtype, rel_l1(pred, pred_ref), abs(loss.item() - loss_ref) / abs(loss_ref)))
+    assert rel_l1(pred, pred_ref) <= (1e-5 if f32 else 1e-2)
+    assert abs(loss.item() - loss_ref) <= (1e-5 if f32 else 1e-3) * abs(loss_ref)
+    for k, prm in model.named_parameters():
+        got = eng.grad_view(prm).detach().float().cpu().reshape(-1)
+        ref = grads_ref[k].reshape(-1).float()
+        if f32:
+            assert max_rel(got, ref) <= 2e-4, (k, max_rel(got, ref))
+        else:
+            cos = float(torch.dot(got, ref) / (got.norm() * ref.norm() + 1e-30))
+            assert cos >= 0.93, (k, cos)
+    for k, v in stats_ref.items():
+        got = model.state_dict()[k].cpu()
+        v = v.float()
+        assert float((got - v).abs().max()) <= (1e-5 if f32 else 2e-2) * float(v.abs().max()) + 1e-6, k
+    # the fused gradient norm: norm partials of the weight gradients + ranges, on levels whose wgrad forms differ from a square's
+    norm_ref = float(torch.sqrt(sum((g_.double() ** 2).sum() for g_ in grads_ref.values())))
+    print('%s: grad norm %.6e (oracle %.6e)' % (dtype, float(tr.state[3]), norm_ref))
+    assert abs(float(tr.state[3]) - norm_ref) <= (1e-4 if f32 else 2e-2) * norm_ref
+    # eval-mode prediction with the weights the step started from
+    model.load_state_dict(p0)
+    model.eval()
+    with torch.no_grad():
+        pe = model(audio.to(DEV))
+    print('%s: eval pred rel-L1 %.3e' % (dtype, rel_l1(pe, pred_eval_ref)))
+    assert rel_l1(pe, pred_eval_ref) <= (1e-5 if f32 else 1e-2)
+    with pytest.raises(RuntimeError, match='not divisible'):          # 200 = 8 * 25: not a multiple of 2^7
+        with torch.no_grad():
+            model(audio[..., :200].contiguous().to(DEV))
 
 
 def test_same_seed_same_weights_and_keys():

@@ -433,3 +433,117 @@ def test_launch_plan_capture_and_replay_state_machine():
     t.ok = True
     t._graphed(mk(5), None, mk(5))
     assert t._plan is not None and t.impl_calls == 3 and t.engine.pins == 1
+
+
+def test_k4_rect_cases_reach_the_forms_they_name():
+    """tests/k4_rect_cases.py (the shapes of tests/test_gpu_k4_rect.py): every igemm case runs the kernel form its table
+    names for each epilogue it launches, every weight-gradient case gets the answers its table holds from the plan queries,
+    every rectangular case stands beside its transposed twin, and the forms add up: each igemm form is reached by RAW
+    (where it can carry it), Z_STATS and BWD on a power-of-two rectangle, on its transpose where the tiling rule allows
+    one, and on a non-power-of-two grid; each weight-gradient route has a non-square and a non-power-of-two case."""
+    import k4_rect_cases as kc
+    itool, wtool = _igemm_plan_tool(), _wgrad_plan_tool()
+    pow2 = lambda n: n & (n - 1) == 0
+    is_pow2 = lambda c: pow2(c['Hs']) and pow2(c['Ws'])
+    reached = {}                                   # (form, geom, epi) -> [case]
+    assert len(kc.IGEMM) >= 100
+    for key, c in kc.IGEMM.items():
+        assert c['Hs'] != c['Ws'], key
+        assert c['B'] * c['Hs'] * c['Ws'] <= 16 * 56 * 40 and max(c['Hs'], c['Ws']) <= 64, key
+        twin = '%s/%s/%dx%dx%d/%s' % (key.split('/')[0], key.split('/')[1], c['B'], c['Ws'], c['Hs'], c['cset'])
+        assert twin in kc.IGEMM, key
+        assert any(f is not None for f in c['forms'].values()), key
+        for epi, form in c['forms'].items():
+            assert (form is None) == (kc.IGEMM[twin]['forms'][epi] is None), key
+            if form is None:
+                continue
+            assert _igemm_form(itool.query_row(kc.igemm_row(key, epi))['plan']) == form, (key, epi)
+            reached.setdefault((form, c['geom'], epi), []).append(c)
+    for name, keys in (('accumulate', kc.BWD_ACCUMULATE), ('mask_from_z', kc.BWD_MASK_FROM_Z), ('sentinel', kc.SWAP_SENTINEL)):
+        for key in keys:
+            assert key in kc.IGEMM and (name == 'sentinel' or kc.IGEMM[key]['forms'][kc.BWD] is not None), (name, key)
+
+    def covered(form, geoms, epis, transpose=True):
+        for epi in epis:
+            cs = [c for g in geoms for c in reached.get((form, g, epi), [])]
+            p2 = [c for c in cs if is_pow2(c)]
+            assert p2, (form, geoms, epi, 'no power-of-two rectangle')
+            assert any(not is_pow2(c) for c in cs), (form, geoms, epi, 'no non-power-of-two grid')
+            if transpose:
+                shapes = {(c['Hs'], c['Ws']) for c in cs}
+                assert any((w, h) in shapes for h, w in shapes), (form, geoms, epi, 'no transposed pair')
+
+    all3 = (kc.RAW, kc.Z_STATS, kc.BWD)
+    for form in ('direct', 'tile 128x128 split', 'tile 128x64 split', 'tile 128x64', 'tile 128x128', 'tile 256x64', 'tile 256x128'):
+        covered(form, (0, 1), all3)
+    # the patch kernel needs Hs % 8 == 0 and Ws % 16 == 0, so the transpose of an 8 x 16-tileable image that is not
+    # 16 x 16-tileable runs another kernel; patch-tall and the ring need 16 on both sides: both orientations run them
+    for geom in (0, 1):
+        covered('patch 128x64', (geom,), all3, transpose=False)
+        for form in ('ring 256x64', 'ring 256x128'):          # (the ring kernel has no RAW epilogue)
+            covered(form, (geom,), (kc.Z_STATS, kc.BWD))
+    covered('patch 128x128', (0,), all3, transpose=False)
+    covered('patch-tall 256x64', (1,), all3)
+    for form, geoms in (('patch 128x64', (0, 1)), ('patch 128x128', (0,))):        # ... and name what their transposes run
+        for c in [c for g in geoms for c in reached[(form, g, kc.RAW)]]:
+            if c['Hs'] % 16 or c['Ws'] % 16:
+                twin = kc.IGEMM['%s/%s/%dx%dx%d/%s' % ('bf16', 'ST'[c['geom']] + '2', c['B'], c['Ws'], c['Hs'], c['cset'])]
+                assert twin['forms'][kc.RAW].startswith('tile') and not twin['forms'][kc.RAW].endswith('split')
+    # accumulate: one BWD launch per form and geometry that has a BWD case; mask_from_z: a ring and a patch case
+    acc_forms = {(kc.IGEMM[k]['forms'][kc.BWD], kc.IGEMM[k]['dtype']) for k in kc.BWD_ACCUMULATE}
+    for (form, geom, epi), cs in reached.items():
+        if epi == kc.BWD:
+            for dt in {c['dtype'] for c in cs}:
+                assert (form, dt) in acc_forms, (form, dt)
+    mz = {kc.IGEMM[k]['forms'][kc.BWD].split()[0] for k in kc.BWD_MASK_FROM_Z}
+    assert mz >= {'ring', 'patch'}
+    sent = {(kc.IGEMM[k]['forms'][kc.RAW], kc.IGEMM[k]['geom']) for k in kc.SWAP_SENTINEL if kc.IGEMM[k]['dtype'] == 1}
+    assert {f for f, g, e in reached if e == kc.RAW and any(c['dtype'] == 1 for c in reached[(f, g, e)])} == {f for f, _ in sent}
+    # two-segment BWD launches: sets B (as B2 / A2) and D
+    assert {c['cset'] for c in kc.IGEMM.values() if len(c['segs']) == 2 and c['forms'][kc.BWD]} >= {'A2', 'B2', 'D'}
+    # 1 x 2 and 2 x 1 (1 x 3, 3 x 1): a split tile, where the one-pixel form at 1 x 1 plans an unsplit T2 tile
+    for hw in ((1, 2), (2, 1), (1, 3), (3, 1)):
+        cs = [c for c in kc.IGEMM.values() if (c['Hs'], c['Ws']) == hw and c['B'] == 32]
+        assert {c['geom'] for c in cs} == {0, 1} and all(f.endswith('split') for c in cs for f in c['forms'].values())
+    onepx = dict(name='', dtype=1, geom=1, B=32, Hs=1, Ws=1, C0=128, C1=0, N=128, epi=0, segs=[128], ks=0)
+    assert _igemm_form(itool.query_row(onepx)['plan']) == 'tile 128x64'
+
+    # ---- weight gradient
+    by_route = {}
+    assert len(kc.WGRAD) >= 80
+    for key, c in kc.WGRAD.items():
+        assert c['Hs'] != c['Ws'] and c['B'] * c['Hs'] * c['Ws'] <= 16 * 56 * 40 and max(c['Hs'], c['Ws']) <= 64, key
+        twin = '%s/%dx%dx%d/%s' % (key.split('/')[0], c['B'], c['Ws'], c['Hs'], key.split('/')[2])
+        assert twin in kc.WGRAD and kc.WGRAD[twin]['route'] == c['route'], key
+        got = wtool.query_row(kc.wgrad_row(c))
+        assert (got['workspace_bytes'], got['sq_count'], got['batchable']) == c['answers'], (key, got)
+        patch = wtool.query_group([kc.wgrad_row(c)])
+        assert (patch >= 0) == c['patch'], (key, patch)
+        ws, sq, cls = c['answers']
+        want = {'fast': ws == 0 and sq > 0 and cls == 2, 'general': ws == 0 and sq > 0 and cls == 1,
+                'direct': (ws, sq, cls) == (0, 0, 0), 'split': ws > 0 and sq > 0 and cls == 0 and patch < 0,
+                'patch': patch == ws > 0 and sq > 0, 'f32 unsplit': ws == 0 and sq > 0 and cls == 0,
+                'f32 split': ws > 0 and sq > 0}[c['route']]
+        assert want and (c['dtype'] == 0) == (c['route'].startswith('f32') or c['route'] == 'direct' and key.startswith('f32')), key
+        if c['route'] == 'fast':
+            assert is_pow2(c)
+        by_route.setdefault(c['route'], []).append(c)
+    assert set(by_route) == set(kc.ROUTES)
+    for route, cs in by_route.items():
+        if route != 'fast':                                    # (the fast form exists for power-of-two images only)
+            assert any(not is_pow2(c) for c in cs), route
+        assert any(c['C1'] for c in cs) or route in ('direct', 'split', 'f32 split'), route      # a second gathered source
+    assert any(c['C1'] and c['route'] == 'patch' for c in kc.WGRAD.values())
+    # the two batch launches: every problem has the class of its launch; groups stand beside their transposes
+    flip = lambda probs: sorted((w, h) + tuple(r) for h, w, *r in probs)
+    for B, cls, probs in kc.WGRAD_BATCH:
+        assert any(flip(probs) == sorted(q) for b, k, q in kc.WGRAD_BATCH if (b, k) == (B, cls))
+        assert any(not (pow2(h) and pow2(w)) for h, w, *_ in probs) == (cls == 1) and all(h != w for h, w, *_ in probs)
+        for prob in probs:
+            got = wtool.query_row(kc.batch_row(B, prob))
+            assert got['batchable'] == cls and got['batch_sq_count'] > 0, prob
+    assert {cls for _, cls, _ in kc.WGRAD_BATCH} == {1, 2}
+    for probs, nbytes in kc.WGRAD_PATCH_BATCH:
+        assert any(flip(probs) == sorted(q) for q, _ in kc.WGRAD_PATCH_BATCH)
+        assert wtool.query_group([kc.batch_row(kc.PATCH_BATCH_B, p) for p in probs]) == nbytes, probs
+        assert any(not (pow2(h) and pow2(w)) for h, w, *_ in probs)
