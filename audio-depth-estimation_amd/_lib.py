@@ -94,6 +94,16 @@ class AdnCoarseLoss(C.Structure):
     ]
 
 
+class AdnDualRegLoss(C.Structure):
+    _fields_ = [
+        ('coarse', c_void_p), ('offset', c_void_p), ('gt', c_void_p), ('n_valid', c_void_p),
+        ('pixels', c_int64), ('pixels_global', c_int64),
+        ('coarse_weight', c_float), ('final_weight', c_float), ('offset_reg_weight', c_float),
+        ('final_depth', c_void_p), ('dcoarse', c_void_p), ('doffset', c_void_p),
+        ('workspace', c_void_p), ('workspace_bytes', c_int64),
+    ]
+
+
 # name -> (restype, argtypes).  Must list every symbol include/adn.h declares
 # (tests/test_abi.py cross-checks this table against the header and the built library).
 _PROTOS = {
@@ -255,6 +265,10 @@ _PROTOS = {
     'adn_coarse_loss': (C.c_int, [C.POINTER(AdnCoarseLoss), c_void_p]),
     'adn_coarse_loss_finish': (C.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p,
                                          c_void_p]),
+    'adn_dualreg_loss_workspace_bytes': (c_int64, [c_int64]),
+    'adn_dualreg_loss': (C.c_int, [C.POINTER(AdnDualRegLoss), c_void_p]),
+    'adn_dualreg_loss_finish': (C.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_float, c_float, c_float,
+                                          c_void_p, c_void_p]),
 }
 
 _lib = None

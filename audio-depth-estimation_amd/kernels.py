@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import AdnAttnDesc, AdnCoarseLoss, AdnDistillSmall  # noqa: E402
+from ._lib import AdnAttnDesc, AdnCoarseLoss, AdnDistillSmall, AdnDualRegLoss  # noqa: E402
 from ._lib import (ADN_BF16, ADN_F32, EPI_ACT, EPI_ADD, EPI_BWD, EPI_FINAL, EPI_RAW, EPI_Z_STATS, GEMM_S1, GEMM_S2, GEMM_T2,
                    AdnEpiSeg, AdnIgemmDesc, AdnMx8ConvDesc, AdnWgradDesc, ptr)
 
@@ -1094,3 +1094,38 @@ def coarse_loss_finish(workspace, pixels, sums, n_valid, pixels_global, ce_weigh
     _dev(workspace, sums, n_valid, terms)
     _lib.call('adn_coarse_loss_finish', ptr(workspace), int(pixels), ptr(sums), ptr(n_valid), int(pixels_global),
               float(ce_weight), float(reg_weight), ptr(terms), _stream())
+
+
+# ---- dual-regression coarse-depth family (csrc/dualreg.hip) --------------------------------------------------------
+def dualreg_loss_workspace_bytes(pixels):
+    return _lib.load().adn_dualreg_loss_workspace_bytes(pixels)
+
+
+def dualreg_loss(coarse, offset, final, gt=None, n_valid=None, pixels_global=None, coarse_weight=1.0, final_weight=1.0,
+                 offset_reg_weight=0.01, dcoarse=None, doffset=None, workspace=None):
+    """coarse / offset f32 [pixels] -> final = coarse + offset; with gt also dcoarse / doffset and the per-block partials in
+    ``workspace``; see adn_dualreg_loss."""
+    pixels = coarse.numel()
+    _dev(coarse, offset, final, gt, n_valid, dcoarse, doffset, workspace)
+    for name, t in (('coarse', coarse), ('offset', offset), ('final', final), ('gt', gt), ('dcoarse', dcoarse),
+                    ('doffset', doffset)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != pixels):
+            raise RuntimeError(f'dualreg_loss: {name} must be contiguous float32 with {pixels} elements')
+    if n_valid is not None and n_valid.dtype != torch.float64:
+        raise RuntimeError('dualreg_loss: n_valid must be float64')
+    d = AdnDualRegLoss()
+    d.coarse, d.offset, d.gt, d.n_valid = ptr(coarse), ptr(offset), ptr(gt), ptr(n_valid)
+    d.pixels, d.pixels_global = pixels, int(pixels_global if pixels_global is not None else pixels)
+    d.coarse_weight, d.final_weight, d.offset_reg_weight = float(coarse_weight), float(final_weight), float(offset_reg_weight)
+    d.final_depth, d.dcoarse, d.doffset = ptr(final), ptr(dcoarse), ptr(doffset)
+    d.workspace, d.workspace_bytes = ptr(workspace), (_nbytes(workspace) if workspace is not None else 0)
+    _lib.call('adn_dualreg_loss', C.byref(d), _stream())
+
+
+def dualreg_loss_finish(workspace, pixels, sums, n_valid, pixels_global, coarse_weight, final_weight, offset_reg_weight,
+                        terms):
+    """workspace None: sums f64[3] are taken as given (all-reduced); terms f32[4] = coarse, final, offset_reg, total (or
+    None)."""
+    _dev(workspace, sums, n_valid, terms)
+    _lib.call('adn_dualreg_loss_finish', ptr(workspace), int(pixels), ptr(sums), ptr(n_valid), int(pixels_global),
+              float(coarse_weight), float(final_weight), float(offset_reg_weight), ptr(terms), _stream())

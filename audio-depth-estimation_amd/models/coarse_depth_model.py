@@ -8,8 +8,10 @@ rgb_depth_model's, so the state_dict keys differ and the classes cannot be share
 ``SoftCrossEntropyLoss`` / ``FocalLoss`` / ``OrdinalRegressionLoss`` with the reference's constructor signatures.
 ``forward(x) -> (logits [B, n_bins, H, W], depth [B, 1, H, W])`` runs as an op tape on libadn (coarse_engine.py); the
 fused coarse_engine.CoarseDepthTrainer is the fast path, the loss modules below serve the reference-style autograd loop
-and ``CoarseDepthTrainer.from_criterion``.  Functional gaps raise NotImplementedError: model_type 'lite' / 'hybrid' /
-'dual_reg', and an input size different from ``output_size`` (the bilinear resize of the logits; train_coarse_depth.py
+and ``CoarseDepthTrainer.from_criterion``.  ``DualRegressionModel`` / ``DualRegressionLoss`` (reference :857-1056, model_type
+'dual_reg' of the script) are constructed directly, as the reference does; they run on dualreg_engine.py.  Functional gaps
+raise NotImplementedError: model_type 'lite' / 'hybrid' (and 'dual_reg' through the factory), ``bilinear=False``, and an
+input size different from ``output_size`` (the bilinear resize of the logits / offset features; train_coarse_depth.py
 always feeds images_size inputs).  ``2 <= n_bins <= 512``; back-propagating through the returned ``depth`` in the autograd
 loop additionally needs ``n_bins <= 256`` (adn_bins_bwd), the fused trainer does not.
 """
@@ -155,6 +157,106 @@ class CoarseDepthUNet(nn.Module):
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
 
 
+class DualRegressionModel(nn.Module):
+    """Pure regression model (reference :857-994): a shared encoder, a coarse regression decoder + 1x1 head, and an offset
+    decoder whose features are fused with the DETACHED coarse depth ([64 + 1] -> 64 -> 32 channels, biased 3x3 convs in
+    front of BatchNorm) before the 1x1 offset head.  ``forward(x) -> (coarse_depth, offset, final_depth)``, each f32
+    [B, 1, H, W], final = coarse + offset.  Constructed directly (the reference's factory does not know it either,
+    train_coarse_depth.py:282-288); ``torch.manual_seed(s)`` before the constructor gives the reference's weights.
+    ``plane_channels``: width of the NHWC record that carries the coarse depth into the fusion conv (None: the engine's
+    default, see dualreg_engine.DualRegEngine)."""
+
+    def __init__(self, input_channels: int = 2, base_channels: int = 64, output_size: int = 256, bilinear: bool = True):
+        super().__init__()
+        if not bilinear:
+            raise NotImplementedError('DualRegressionModel(bilinear=False) is not implemented (no reference caller builds it)')
+        self.output_size = output_size
+        self.input_channels = input_channels
+        self.base_channels = base_channels
+        factor = 2 if bilinear else 1
+        self.inc = DoubleConv(input_channels, base_channels)
+        self.down1 = Down(base_channels, base_channels * 2)
+        self.down2 = Down(base_channels * 2, base_channels * 4)
+        self.down3 = Down(base_channels * 4, base_channels * 8)
+        self.down4 = Down(base_channels * 8, base_channels * 16 // factor)
+        self.coarse_up1 = Up(base_channels * 16, base_channels * 8 // factor, bilinear)
+        self.coarse_up2 = Up(base_channels * 8, base_channels * 4 // factor, bilinear)
+        self.coarse_up3 = Up(base_channels * 4, base_channels * 2 // factor, bilinear)
+        self.coarse_up4 = Up(base_channels * 2, base_channels, bilinear)
+        self.coarse_head = nn.Conv2d(base_channels, 1, kernel_size=1)
+        self.offset_up1 = Up(base_channels * 16, base_channels * 8 // factor, bilinear)
+        self.offset_up2 = Up(base_channels * 8, base_channels * 4 // factor, bilinear)
+        self.offset_up3 = Up(base_channels * 4, base_channels * 2 // factor, bilinear)
+        self.offset_up4 = Up(base_channels * 2, base_channels, bilinear)
+        self.offset_fusion = nn.Sequential(
+            nn.Conv2d(base_channels + 1, base_channels, 3, padding=1),
+            nn.BatchNorm2d(base_channels),
+            nn.ReLU(inplace=True),
+            nn.Conv2d(base_channels, base_channels // 2, 3, padding=1),
+            nn.BatchNorm2d(base_channels // 2),
+            nn.ReLU(inplace=True),
+        )
+        self.offset_head = nn.Conv2d(base_channels // 2, 1, kernel_size=1)
+        self._init_weights()
+        self._engine = None
+        self.compute_dtype = default_compute_dtype()
+        self.plane_channels = None
+
+    def _init_weights(self):
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+
+    def engine(self):
+        from ..dualreg_engine import DualRegEngine
+        e = self._engine
+        if e is None or e.requested_dtype != self.compute_dtype or e.requested_plane != self.plane_channels:
+            object.__setattr__(self, '_engine', DualRegEngine(self, self.compute_dtype, self.plane_channels))
+        return self._engine
+
+    def forward(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """x [B, C, S, S] -> (coarse_depth, offset, final_depth).  In training mode under autograd all three hang off one
+        autograd node, so the reference's ``criterion(*model(x), gt)[0].backward()`` loop works."""
+        from ..dualreg_engine import run_dualreg
+        return run_dualreg(self.engine(), x, self.training)
+
+    def predict_depth(self, x: torch.Tensor) -> torch.Tensor:
+        return self.forward(x)[2]
+
+    def get_num_params(self) -> int:
+        return sum(p.numel() for p in self.parameters() if p.requires_grad)
+
+
+class DualRegressionLoss(nn.Module):
+    """L1 of the coarse depth + L1 of the final depth on gt > 0 (every pixel when none is valid) + mean |offset|
+    (reference :997-1056).  Plain torch; dualreg_engine.DualRegressionTrainer.from_criterion reads the weights."""
+
+    def __init__(self, coarse_weight: float = 1.0, final_weight: float = 1.0, offset_reg_weight: float = 0.01):
+        super().__init__()
+        self.coarse_weight = coarse_weight
+        self.final_weight = final_weight
+        self.offset_reg_weight = offset_reg_weight
+
+    def forward(self, coarse_depth: torch.Tensor, offset: torch.Tensor, final_depth: torch.Tensor,
+                target_depth: torch.Tensor) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+        valid_mask = target_depth > 0
+        if valid_mask.any():
+            coarse_loss = F.l1_loss(coarse_depth[valid_mask], target_depth[valid_mask])
+            final_loss = F.l1_loss(final_depth[valid_mask], target_depth[valid_mask])
+        else:
+            coarse_loss = F.l1_loss(coarse_depth, target_depth)
+            final_loss = F.l1_loss(final_depth, target_depth)
+        offset_reg = offset.abs().mean()
+        total_loss = (self.coarse_weight * coarse_loss + self.final_weight * final_loss +
+                      self.offset_reg_weight * offset_reg)
+        return total_loss, {'total': total_loss, 'coarse': coarse_loss, 'final': final_loss, 'offset_reg': offset_reg}
+
+
 # ---- loss modules (reference :294-468); plain torch on whatever device their inputs live on ---------------------------
 class OrdinalRegressionLoss(nn.Module):
     """Ordinal regression loss (reference :294-321; no caller uses it)."""
@@ -279,7 +381,8 @@ def init_net(net, init_type='kaiming', init_gain=0.02, gpu_ids=[]):
 _UNBUILT = {
     'lite': "model_type 'lite' (CoarseDepthLite: k4 s2 conv / transposed-conv stack with biases) is not implemented",
     'hybrid': "model_type 'hybrid' (CoarseWithOffsetModel: second decoder + offset head) is not implemented",
-    'dual_reg': "model_type 'dual_reg' (DualRegressionModel: two regression decoders) is not implemented",
+    'dual_reg': "model_type 'dual_reg' is not built by this factory (nor by the reference's): construct "
+                "DualRegressionModel directly, as train_coarse_depth does",
 }
 
 

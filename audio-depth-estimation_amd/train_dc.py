@@ -437,13 +437,17 @@ def warm_restart_lr(epoch, base_lr, T_0=20, T_mult=2, eta_min=1e-6):
 
 
 def main_coarse(argv=None):
-    """/root/reference/train_coarse_depth.py:133-645 for model_type 'unet': CoarseDepthUNet, CoarseDepthLoss (soft CE, or
-    focal with --use_focal) with valid = depth > 0, AdamW(wd 0.01) / Adam / SGD(momentum 0.9), clip_grad_norm_(1.0),
-    CosineAnnealingWarmRestarts(20, 2, 1e-6) per epoch; checkpoints ./checkpoints/<experiment>/checkpoint_N.pth and
-    best.pth with {epoch, state_dict, optimizer, bin_centers, bin_edges}.  Targets are binned on the device."""
+    """The reference's train_coarse_depth.py:133-645 for model_type 'unet' and 'dual_reg'.  'unet': CoarseDepthUNet,
+    CoarseDepthLoss (soft CE, or focal with --use_focal) with valid = depth > 0, targets binned on the device.  'dual_reg':
+    DualRegressionModel constructed directly (:282-288), DualRegressionLoss(--coarse_weight, --final_weight,
+    --offset_reg_weight), no bin centres on the model, validation on the final depth.  Both: AdamW(wd 0.01) / Adam /
+    SGD(momentum 0.9), clip_grad_norm_(1.0), CosineAnnealingWarmRestarts(20, 2, 1e-6) per epoch; checkpoints
+    ./checkpoints/<experiment>/checkpoint_N.pth and best.pth with {epoch, state_dict, optimizer, bin_centers, bin_edges}."""
     from .coarse_engine import CoarseDepthTrainer
     from .dataloader.utils_dataset import compute_bins
-    from .models.coarse_depth_model import CoarseDepthLoss, define_coarse_depth_model
+    from .dualreg_engine import DualRegressionTrainer
+    from .models.coarse_depth_model import (CoarseDepthLoss, DualRegressionLoss, DualRegressionModel,
+                                            define_coarse_depth_model)
     p = argparse.ArgumentParser(description='Train Coarse Depth Classification Model (MI355X)')
     p.add_argument('--dataset', type=str, default='batvisionv2', choices=['batvisionv1', 'batvisionv2'])
     p.add_argument('--sparse_method', type=str, default='downup_015')
@@ -485,21 +489,39 @@ def main_coarse(argv=None):
     args.device, args.num_workers, args.seed = 'cuda', 0, 42
     dev = _device(args, local if world > 1 else None)
     say = print if rank == 0 else (lambda *a, **k: None)
-    model = define_coarse_depth_model(model_type=args.model_type, input_channels=2, n_bins=args.n_bins,
-                                      base_channels=args.base_channels, output_size=S)
+    dual = args.model_type == 'dual_reg'
+    if dual:                # the reference's factory does not know it either: constructed directly (:282-288)
+        model = DualRegressionModel(input_channels=2, base_channels=args.base_channels, output_size=S)
+    else:
+        model = define_coarse_depth_model(model_type=args.model_type, input_channels=2, n_bins=args.n_bins,
+                                          base_channels=args.base_channels, output_size=S)
     edges, centers = compute_bins(args.n_bins, args.bin_mode, None, md, args.sid_alpha)
     norm = md if cfg.dataset.depth_norm else 1.0
     model.compute_dtype = PRECISIONS[args.precision]
     model = model.to(dev).train()
-    model.set_bin_centers((centers / norm).to(dev))
+    if not dual:
+        model.set_bin_centers((centers / norm).to(dev))
     dev_edges = (edges / norm).to(dev)
     say(f'Experiment: {exp}\nParameters: {model.get_num_params():,}')
-    criterion = CoarseDepthLoss(n_bins=args.n_bins, ce_weight=args.ce_weight, regression_weight=args.regression_weight,
-                                use_focal=args.use_focal, use_soft_ce=not args.use_focal, soft_ce_sigma=args.soft_ce_sigma)
     eng = model.engine()
-    trainer = CoarseDepthTrainer.from_criterion(eng, criterion, optimizer=args.optimizer, lr=args.learning_rate,
-                                                weight_decay=0.01 if args.optimizer == 'AdamW' else 0.0, clip_norm=1.0,
-                                                ddp=reducer)
+    opt_kw = dict(optimizer=args.optimizer, lr=args.learning_rate, weight_decay=0.01 if args.optimizer == 'AdamW' else 0.0,
+                  clip_norm=1.0, ddp=reducer)
+    if dual:
+        say('  - Dual regression model (coarse reg + offset reg)')
+        criterion = DualRegressionLoss(coarse_weight=args.coarse_weight, final_weight=args.final_weight,
+                                       offset_reg_weight=args.offset_reg_weight)
+        trainer = DualRegressionTrainer.from_criterion(eng, criterion, **opt_kw)
+        step = lambda audio, gt: trainer.step(audio, gt / norm)
+        predict = lambda mm, b: mm.engine().forward_net(b[0], False)[2] * norm
+        line = lambda m: f'total={m[3]:.4f}, coarse={m[0]:.4f}, final={m[1]:.4f}, off={m[2]:.4f}'
+    else:
+        criterion = CoarseDepthLoss(n_bins=args.n_bins, ce_weight=args.ce_weight, regression_weight=args.regression_weight,
+                                    use_focal=args.use_focal, use_soft_ce=not args.use_focal,
+                                    soft_ce_sigma=args.soft_ce_sigma)
+        trainer = CoarseDepthTrainer.from_criterion(eng, criterion, **opt_kw)
+        step = lambda audio, gt: trainer.step(audio, None, gt / norm, edges=dev_edges)
+        predict = lambda mm, b: mm.engine().forward_net(b[0], False)[1] * norm
+        line = lambda m: f'total={m[2]:.4f}, ce={m[0]:.4f}, reg={m[1]:.4f}'
     if args.graph:
         trainer.enable_graph(after_steps=3)
     tl, vl, sampler, fe = _loaders(cfg, args, 'audio', rank, world)
@@ -525,14 +547,14 @@ def main_coarse(argv=None):
         t0, acc = time.time(), []
         for batch in tl:
             audio, gt = _to_device(batch, dev, fe)
-            _, terms = trainer.step(audio, None, gt / norm, edges=dev_edges)
+            _, terms = step(audio, gt)
             acc.append(terms.detach().clone())
-        m = torch.stack(acc).mean(0).tolist() if acc else [float('nan')] * 3
-        say(f'Epoch {epoch}: total={m[2]:.4f}, ce={m[0]:.4f}, reg={m[1]:.4f}, time={time.time() - t0:.1f}s')
+        m = torch.stack(acc).mean(0).tolist() if acc else [float('nan')] * 4
+        say(f'Epoch {epoch}: {line(m)}, time={time.time() - t0:.1f}s')
         state = {'epoch': epoch, 'state_dict': model.state_dict(), 'optimizer': trainer.state_dict(),
                  'bin_centers': centers, 'bin_edges': edges}
         if args.validation and epoch % args.validation_iter == 0:
-            errs = _validate(model, vl, dev, lambda mm, b: mm.engine().forward_net(b[0], False)[1] * norm, fe)
+            errs = _validate(model, vl, dev, predict, fe)
             say(f'Val - RMSE: {errs["rmse"]:.3f}, ABS_REL: {errs["abs_rel"]:.3f}, Delta1: {errs["delta1"]:.3f}')
             if errs['rmse'] < best:
                 best = errs['rmse']

@@ -683,6 +683,39 @@ int adn_coarse_loss(const AdnCoarseLoss* d, void* stream);
 int adn_coarse_loss_finish(const void* workspace, int64_t pixels, double* sums, const double* n_valid,
                            int64_t pixels_global, float ce_weight, float reg_weight, float* terms, void* stream);
 
+/* Dual-regression coarse-depth family (DualRegressionModel / DualRegressionLoss, models/coarse_depth_model.py): the loss
+ * tail behind the two 1x1 heads.  f32 arithmetic, f64 final reductions, no atomics, bit-reproducible.
+ *
+ * adn_dualreg_loss: ONE pass over `pixels` elements.  final_depth = coarse + offset (f32 add, always written).  With gt
+ * (needs dcoarse, doffset, n_valid = device f64[1] GLOBAL count of gt > 0, workspace): mask m = gt > 0, n = n_valid; when
+ * n_valid == 0 the reference's unmasked branch applies, m = 1 and n = pixels_global.  Per-block f64 partials of
+ * sum m |coarse - gt|, sum m |final - gt|, sum |offset| go into the workspace, and
+ *   dcoarse = (coarse_weight sgn(coarse - gt) + final_weight sgn(final - gt)) m / n
+ *   doffset = final_weight sgn(final - gt) m / n + offset_reg_weight sgn(offset) / pixels_global
+ * with sgn(0) = 0: the gradient of coarse_weight L1(coarse) + final_weight L1(final) + offset_reg_weight mean|offset|
+ * (the coarse depth is NOT detached in final = coarse + offset).  gt == NULL: final_depth alone (inference). */
+typedef struct {
+  const float* coarse;               /* [pixels] */
+  const float* offset;               /* [pixels] */
+  const float* gt;                   /* [pixels] or NULL (forward only) */
+  const double* n_valid;
+  int64_t pixels, pixels_global;     /* pixels_global: pixel count of the global batch under data parallelism */
+  float coarse_weight, final_weight, offset_reg_weight;
+  float* final_depth;                /* [pixels] */
+  float* dcoarse;                    /* [pixels], with gt */
+  float* doffset;                    /* [pixels], with gt */
+  void* workspace;
+  int64_t workspace_bytes;
+} AdnDualRegLoss;
+int64_t adn_dualreg_loss_workspace_bytes(int64_t pixels);
+int adn_dualreg_loss(const AdnDualRegLoss* d, void* stream);
+/* workspace != NULL: reduce the partials adn_dualreg_loss left for `pixels` pixels into sums f64[3]; NULL: take sums as
+ * given (all-reduced by the caller).  terms != NULL: terms f32[4] = (coarse = sums[0] / n, final = sums[1] / n,
+ * offset_reg = sums[2] / pixels_global, total = the weighted sum), n = n_valid, or pixels_global when n_valid == 0. */
+int adn_dualreg_loss_finish(const void* workspace, int64_t pixels, double* sums, const double* n_valid,
+                            int64_t pixels_global, float coarse_weight, float final_weight, float offset_reg_weight,
+                            float* terms, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
