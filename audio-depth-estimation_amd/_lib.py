@@ -163,6 +163,7 @@ _PROTOS = {
     'adn_attn_fwd': (C.c_int, [C.POINTER(AdnAttnDesc), c_void_p]),
     'adn_attn_bwd_workspace_bytes': (c_int64, [C.POINTER(AdnAttnDesc)]),
     'adn_attn_bwd': (C.c_int, [C.POINTER(AdnAttnDesc), c_void_p]),
+    'adn_attn_form': (C.c_int, [C.POINTER(AdnAttnDesc), c_int32]),
     'adn_channel_sum_workspace_bytes': (c_int64, [c_int64, c_int32]),
     'adn_channel_sum': (C.c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
     'adn_gate_bwd': (C.c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,

@@ -9,7 +9,7 @@
 //   backward (recompute P from lse):  D = rowsum(dO * O),  dS = P * (dO V^T - D) * scale,
 //                                     dQ = dS K,  dK = dS^T Q,  dV = P^T dO
 //
-// This file holds the generic kernels (any dqk <= 64, dv <= 512, f32 or bf16 storage, f32 arithmetic):
+// This file holds the generic kernels (any dqk <= 128, dv <= 1024, f32 or bf16 storage, f32 arithmetic, any scale):
 // one wave per query (forward, dQ) or per key (dK/dV), 64 keys / queries per inner step, probabilities
 // exchanged through LDS.  The bf16 MFMA kernels for the full-width head dims live in attn_mfma.hip.
 #include "adn_common.h"
@@ -371,6 +371,13 @@ AttnParams to_params(const AdnAttnDesc* d) {
 
 int adn_attn_mfma_fwd(const AdnAttnDesc* d, hipStream_t st);   // attn_mfma.hip: returns 1 if it took the launch
 int adn_attn_mfma_bwd(const AdnAttnDesc* d, hipStream_t st);
+int adn_attn_mfma_qt(const AdnAttnDesc* d, bool bwd);          // the eligibility test both of them start with
+
+extern "C" int adn_attn_form(const AdnAttnDesc* d, int32_t bwd) {
+  int rc = avalidate(d, bwd != 0);
+  if (rc != ADN_OK) return rc;
+  return adn_attn_mfma_qt(d, bwd != 0) != 0 ? 1 : 0;
+}
 
 extern "C" int adn_attn_fwd(const AdnAttnDesc* d, void* stream) {
   int rc = avalidate(d, false);

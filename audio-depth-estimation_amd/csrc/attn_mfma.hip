@@ -146,7 +146,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_mfma_kernel(FParams p) {
   auto softmax_tile = [&](f32x4_t (&st)[QT][4], bf16x8_t (&pa)[QT][2], float (&al)[QT]) {
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
-      float mx = -INFINITY;           // the scale is positive: take the maximum of the raw scores, scale it once
+      float mx = -INFINITY;           // scale > 0 (adn_attn_mfma_qt): take the maximum of the raw scores, scale it once
 #pragma unroll
       for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -591,10 +591,14 @@ static bool attn_generic_forced() {   // ADN_ATTN_GENERIC: test knob, read once
   return forced;
 }
 
-// returns 1 when the MFMA kernel took the launch, 0 when the caller must use the generic path
-int adn_attn_mfma_fwd(const AdnAttnDesc* d, hipStream_t st) {
+// The one eligibility test of the MFMA kernels, shared by both launches and by adn_attn_form (attn.hip): the query-block
+// factor QT of the kernel that takes this descriptor, 0 when it has to run on the generic kernels.  The softmax takes the
+// maximum of the RAW scores and scales it once, which is the maximum of the scaled scores only for a positive scale; the
+// backward divides by the scale.  A non-positive scale is therefore generic.
+int adn_attn_mfma_qt(const AdnAttnDesc* d, bool bwd) {
   if (d->dtype != ADN_BF16) return 0;
   if (attn_generic_forced()) return 0;
+  if (!(d->scale > 0.f)) return 0;
   int qt;
   if (d->dqk == 16 && d->dv == 128) qt = 2;
   else if (d->dqk == 32 && d->dv == 256) qt = 2;
@@ -603,6 +607,13 @@ int adn_attn_mfma_fwd(const AdnAttnDesc* d, hipStream_t st) {
   if (d->N % (64 * qt) != 0) return 0;
   if ((d->ld_q | d->ld_k | d->ld_v) & 7) return 0;                      // 16-byte rows for the DMA / 8-byte frags
   if (!aligned16(d->q) || !aligned16(d->k) || !aligned16(d->v)) return 0;
+  if (bwd && ((d->ld_do & 7) || !aligned16(d->dout))) return 0;
+  return qt;
+}
+
+// returns 1 when the MFMA kernel took the launch, 0 when the caller must use the generic path
+int adn_attn_mfma_fwd(const AdnAttnDesc* d, hipStream_t st) {
+  if (adn_attn_mfma_qt(d, false) == 0) return 0;
   FParams p;
   p.q = reinterpret_cast<const uint16_t*>(d->q);
   p.k = reinterpret_cast<const uint16_t*>(d->k);
@@ -622,16 +633,7 @@ int adn_attn_mfma_fwd(const AdnAttnDesc* d, hipStream_t st) {
 
 // d->workspace already holds D = rowsum(dO * O) (attn.hip computes it before calling)
 int adn_attn_mfma_bwd(const AdnAttnDesc* d, hipStream_t st) {
-  if (d->dtype != ADN_BF16) return 0;
-  if (attn_generic_forced()) return 0;
-  int qt;
-  if (d->dqk == 16 && d->dv == 128) qt = 2;
-  else if (d->dqk == 32 && d->dv == 256) qt = 2;
-  else if (d->dqk == 64 && d->dv == 512) qt = 1;
-  else return 0;
-  if (d->N % (64 * qt) != 0) return 0;
-  if ((d->ld_q | d->ld_k | d->ld_v | d->ld_do) & 7) return 0;
-  if (!aligned16(d->q) || !aligned16(d->k) || !aligned16(d->v) || !aligned16(d->dout)) return 0;
+  if (adn_attn_mfma_qt(d, true) == 0) return 0;
   BParams p;
   p.q = reinterpret_cast<const uint16_t*>(d->q);
   p.k = reinterpret_cast<const uint16_t*>(d->k);

@@ -780,6 +780,15 @@ def attn_bwd(q, k, v, o, lse, dqk, dv, kv_shift, scale, dout, dq, dk, dvg, works
     _lib.annotate(label='attn_bwd', flops=2.0 * d.B2 * d.N * d.N * (3 * dqk + 2 * dv))
 
 
+def attn_form(q, k, v, o, lse, dqk, dv, kv_shift, scale, dout=None, dq=None, dk=None, dvg=None, workspace=None):
+    """Kernel form of attn_fwd (no dout) / attn_bwd (with the gradient operands) on these operands: 'mfma' or 'generic'."""
+    d = _attn_desc(q, k, v, o, lse, dqk, dv, kv_shift, scale, dout, dq, dk, dvg, workspace)
+    form = _lib.load().adn_attn_form(C.byref(d), int(dout is not None))
+    if form < 0:
+        _lib.check(form, 'adn_attn_form')
+    return ('generic', 'mfma')[form]
+
+
 def channel_sum_workspace_bytes(rows, Cc):
     return _lib.load().adn_channel_sum_workspace_bytes(rows, Cc)
 

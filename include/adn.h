@@ -308,6 +308,11 @@ typedef struct {
 int adn_attn_fwd(const AdnAttnDesc* d, void* stream);
 int64_t adn_attn_bwd_workspace_bytes(const AdnAttnDesc* d);
 int adn_attn_bwd(const AdnAttnDesc* d, void* stream);
+/* Host only: the kernel form adn_attn_fwd (bwd = 0) / adn_attn_bwd (bwd != 0) runs for this descriptor, answered by
+ * the launches' own dispatch test: 1 = the bf16 MFMA kernels ((dqk, dv) in {(16,128), (32,256), (64,512)}, N a multiple
+ * of the query block, 16-byte aligned q / k / v (/ dout) rows, scale > 0), 0 = the generic kernels, < 0 = a descriptor
+ * the launch refuses (adn_last_error says why).  Nothing is dereferenced. */
+int adn_attn_form(const AdnAttnDesc* d, int32_t bwd);
 /* out[c] = sum over rows of x[row][c], x [rows][ld] (bias gradients of the 1x1 projections). */
 int64_t adn_channel_sum_workspace_bytes(int64_t rows, int32_t C);
 int adn_channel_sum(const void* x, int64_t rows, int32_t C, int32_t ld, int32_t dtype, float* out,

@@ -547,3 +547,100 @@ def test_k4_rect_cases_reach_the_forms_they_name():
         assert any(flip(probs) == sorted(q) for q, _ in kc.WGRAD_PATCH_BATCH)
         assert wtool.query_group([kc.batch_row(kc.PATCH_BATCH_B, p) for p in probs]) == nbytes, probs
         assert any(not (pow2(h) and pow2(w)) for h, w, *_ in probs)
+
+
+def _attn_fake_desc(row, family, bwd):
+    """The descriptor tests/test_gpu_attention.py builds for a row, with made-up pointers of the same alignment: every buffer
+    starts 256-byte aligned, the views start where attn_cases.view_offsets puts them.  Nothing is dereferenced."""
+    import attn_cases as ac
+    from audio_depth_estimation_amd import _lib
+    d = _lib.AdnAttnDesc()
+    d.dtype, d.B2, d.N, d.dqk, d.dv, d.kv_shift = row['dtype'], row['B2'], row['N'], row['dqk'], row['dv'], row['kv_shift']
+    d.scale = ac.scale_of(row, family)
+    offs = ac.view_offsets(row)
+    base = {b: 0x7f0000000000 + 0x10000000 * i for i, b in enumerate(sorted(ac.layout(row)[0]))}
+    addr = lambda op: base[offs[op][0]] + offs[op][1] * ac.ESIZE[row['dtype']]
+    d.q, d.k, d.v, d.o = addr('q'), addr('k'), addr('v'), addr('o')
+    d.ld_q, d.ld_k, d.ld_v, d.ld_o = (offs[op][2] for op in ('q', 'k', 'v', 'o'))
+    d.lse = 0x7e0000000000 + 4 * ac.GUARD_F32
+    if bwd:
+        d.dout, d.dq, d.dk, d.dvp = addr('dout'), addr('dq'), addr('dk'), addr('dv')
+        d.ld_do, d.ld_dq, d.ld_dk, d.ld_dv = (offs[op][2] for op in ('dout', 'dq', 'dk', 'dv'))
+        d.workspace = 0x7d0000000000 + 4 * ac.GUARD_F32
+        d.workspace_bytes = row['B2'] * row['N'] * 4
+    return d
+
+
+def test_attn_cases_reach_the_forms_they_name():
+    """tests/attn_cases.py (the cases of tests/test_gpu_attention.py): adn_attn_form, the launches' own dispatch predicate,
+    answers the form every row names, forward and backward, for every family the row runs with; the table holds what the
+    issue of the module asks of it; descriptors the launches refuse are refused with a message."""
+    import ctypes
+    import attn_cases as ac
+    from audio_depth_estimation_amd import _lib
+    lib = _lib.load()
+    code = {ac.GENERIC: 0, ac.MFMA: 1}
+    for name, row in ac.ROWS.items():
+        for family in row['families']:
+            for bwd in (0, 1):
+                got = lib.adn_attn_form(ctypes.byref(_attn_fake_desc(row, family, bwd)), bwd)
+                assert got == code[ac.form_of(row, family, bwd)], (name, family, bwd, got, lib.adn_last_error())
+        # eight distinct strides; multiples of 8 wherever the form is (or is one change away from) MFMA
+        lds = [ld for _, _, ld in ac.view_offsets(row).values()]
+        if row['recipe'] != 'fused':
+            assert len(set(lds)) == 8, name
+        if row['recipe'] == 'aligned':
+            assert all(ld % 8 == 0 for ld in lds), name
+        for op, (_, off, ld) in ac.view_offsets(row).items():
+            assert off % ld + ac.width_of(row, op) <= ld, (name, op)
+    rows = ac.ROWS.values()
+    mfma = [r for r in rows if r['form'] == (ac.MFMA, ac.MFMA)]
+    assert all(r['dtype'] == ac.BF16 for r in mfma) and len(mfma) == len(ac.MFMA_ROWS)
+    for dims, ns in zip(ac.MFMA_DIMS, ((128, 384), (128, 384), (64, 192))):
+        mine = [r for r in mfma if (r['dqk'], r['dv']) == dims]
+        assert {r['N'] for r in mine} == set(ns), dims
+        assert {(r['B2'], r['kv_shift']) for r in mine} >= {(3, 1), (3, 2)}, dims
+        assert any(r['recipe'] == 'fused' for r in mine), dims
+        assert any(r['families'] == ('neg-scale',) and (r['dqk'], r['dv']) == dims for r in rows), dims
+    assert {(r['B2'], r['kv_shift']) for r in mfma} == set(ac.SHIFTS)
+    # fallback rows: the MFMA row with one thing changed
+    base = ac.ROWS[ac.FALLBACK_OF]
+    changed = lambda r: [k for k in ('B2', 'N', 'dqk', 'dv', 'kv_shift', 'dtype', 'recipe', 'families') if r[k] != base[k]]
+    for name, key in (('f16-192-n', 'N'), ('f16-128-ldq', 'recipe'), ('f16-128-koff', 'recipe'), ('f16-128-dooff', 'recipe'),
+                      ('f16-128-neg', 'families')):
+        assert changed(ac.ROWS[name]) == [key], name
+    assert ac.ROWS['f16-128-dooff']['form'] == (ac.MFMA, ac.GENERIC)
+    assert ac.view_offsets(ac.ROWS['f16-128-ldq'])['q'][2] % 8 == 4
+    assert ac.view_offsets(ac.ROWS['f16-128-koff'])['k'][1] % 8 == 4 and ac.view_offsets(ac.ROWS['f16-128-dooff'])['dout'][1] % 8 == 4
+    # generic rows: both dtypes, every N and head-dim pair, 1, 2 and 3 dead waves, the limits at N = 16 and 70, the long rowdot
+    for dt in (ac.F32, ac.BF16):
+        gen = [r for r in rows if r['dtype'] == dt and r['recipe'] in ('ragged', 'fused') and r['form'] == (ac.GENERIC, ac.GENERIC)]
+        assert {r['N'] for r in gen} >= {1, 3, 5, 63, 65, 130}
+        assert {(-r['N']) % 4 for r in gen if r['N'] > 1} == {0, 1, 2, 3} and all(r['N'] % 4 or r['N'] == 16 for r in gen)
+        assert {(r['dqk'], r['dv']) for r in gen} >= set(ac.GENERIC_DIMS)
+        assert {r['N'] for r in gen if (r['dqk'], r['dv']) == (128, 1024)} == {16, 70}
+        assert {(r['B2'], r['kv_shift']) for r in gen} >= set(ac.SHIFTS)
+        assert any(r['B2'] * r['N'] > 4096 * 4 and (r['B2'], r['N'], r['dqk'], r['dv']) == (16, 1030, 2, 8) for r in gen)
+    for name in list(ac.OFFSET_ROWS) + list(ac.CHAINED_ROWS) + list(ac.MFMA_ROWS):
+        assert name in ac.ROWS, name
+    assert {(ac.ROWS[n]['dqk'], ac.ROWS[n]['dv']) for n in ac.OFFSET_ROWS} == set(ac.MFMA_DIMS) | set(ac.GENERIC_DIMS)
+    assert {ac.ROWS[n]['form'][0] for n in ac.CHAINED_ROWS} == {ac.MFMA, ac.GENERIC}
+
+    # ---- refusals: a negative answer and a message
+    def refused(bwd, **change):
+        d = _attn_fake_desc(base, 'soft', bwd)
+        for k, v in change.items():
+            setattr(d, k, v)
+        lib.adn_attn_form(ctypes.byref(_attn_fake_desc(base, 'soft', bwd)), bwd)       # (a good call in between)
+        rc = lib.adn_attn_form(ctypes.byref(d), bwd)
+        return rc < 0 and lib.adn_last_error().startswith(b'adn_attn')
+    assert lib.adn_attn_form(ctypes.byref(_attn_fake_desc(base, 'soft', 1)), 1) == 1
+    for bwd in (0, 1):
+        assert refused(bwd, dqk=129), bwd
+        assert refused(bwd, dv=1025, ld_v=2048, ld_o=2048, ld_do=2048, ld_dv=2048), bwd
+        assert refused(bwd, kv_shift=base['B2']), bwd
+        assert refused(bwd, kv_shift=-1), bwd
+        assert refused(bwd, ld_v=base['dv'] - 1), bwd
+    assert refused(1, workspace_bytes=base['B2'] * base['N'] * 4 - 4)
+    assert not refused(0, workspace_bytes=0)                                           # (the forward has no workspace)
+    assert lib.adn_attn_form(None, 0) < 0
