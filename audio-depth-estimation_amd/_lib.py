@@ -120,6 +120,7 @@ _PROTOS = {
     'adn_wgrad_batchable': (c_int32, [C.POINTER(AdnWgradDesc)]),
     'adn_wgrad_batch_sq_count': (c_int32, [C.POINTER(AdnWgradDesc)]),
     'adn_wgrad_batch': (C.c_int, [C.POINTER(AdnWgradDesc), c_int32, c_void_p]),
+    'adn_wgrad_multi': (C.c_int, [C.POINTER(AdnWgradDesc), c_int32, c_void_p]),
     'adn_wgrad_patch_batch_workspace_bytes': (c_int64, [C.POINTER(AdnWgradDesc), c_int32]),
     'adn_wgrad_patch_batch': (C.c_int, [C.POINTER(AdnWgradDesc), c_int32, c_void_p]),
     'adn_wgrad_sq_count': (c_int32, [C.POINTER(AdnWgradDesc)]),

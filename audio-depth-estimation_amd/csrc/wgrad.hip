@@ -49,7 +49,7 @@ __device__ __forceinline__ int swz_f(int row) { return (row & 3) | (((row >> 3) 
 
 // (the body is shared by the one-problem kernel and the multi-problem launch of the small-image layers: `bid` is the
 //  workgroup index inside its problem)
-template <typename T, bool FAST, bool MIXED, bool S1, bool HALF>
+template <typename T, bool FAST, bool MIXED, bool S1, bool HALF, bool SMALL = false>
 __device__ __forceinline__ void wgrad_mfma_body(const WParams& p, const int bid) {
 #if defined(__HIP_DEVICE_COMPILE__)   // buffer-resource builtins exist only in the device pass
   constexpr int EPC = 16 / (int)sizeof(T);
@@ -129,13 +129,26 @@ __device__ __forceinline__ void wgrad_mfma_body(const WParams& p, const int bid)
     }
   }
 
+  // SMALL, 1x1 images: only the taps (ky, kx) in {1,2}^2 can be in range.  A workgroup whose column tile holds none of
+  // them runs no pixel step at all: its accumulators stay +0.0f, which is what the staged zeros would have summed to
+  bool dead = false;
+  if constexpr (SMALL) {
+    if (Hs == 1 && Ws == 1) {
+      dead = true;
+      for (int t = tile_c * 128 / C; t <= (tile_c * 128 + 127) / C; ++t)
+        dead = dead && (((t >> 2) - 1u) > 1u || ((t & 3) - 1u) > 1u);
+    }
+  }
   const int s_begin = (int)(((int64_t)p.steps * split) / p.nsplit);
-  const int s_end = (int)(((int64_t)p.steps * (split + 1)) / p.nsplit);
+  const int s_end = dead ? s_begin : (int)(((int64_t)p.steps * (split + 1)) / p.nsplit);
 
   typedef const __attribute__((address_space(1))) void* gptr_t;
   typedef __attribute__((address_space(3))) void* lptr_t;
 
   // ---- FAST addressing (power-of-two image, >= BKP pixels per image, tile-uniform sources) ----
+  // SMALL (k4, bf16): the same split for power-of-two images of FEWER than BKP pixels.  A step covers BKP / (Hs*Ws) whole
+  // images, so the image row and column of pixel m = s*BKP + r depend on r alone: every border test is a lane constant
+  // (folded into m_c), and the only per-step test left is the partial last step (rows at or beyond Msmall read as zeros).
   // address = descriptor base (SGPR) + voffset (per lane, constant over the pixel loop) + soffset (scalar per
   // step).  For pixel m = s*BKP + r the gathered pixel (2i, 2j) has linear index 4m - 2j, which splits into a
   // scalar part of s and a lane constant of r; border taps are recognised by scalar compares combined with
@@ -143,7 +156,7 @@ __device__ __forceinline__ void wgrad_mfma_body(const WParams& p, const int bid)
   constexpr unsigned OOB = 0x80000000u;
   constexpr int ESZ = (int)sizeof(T);
   unsigned pvoff[PASSES], gvoff[PASSES];
-  bool m_y0[PASSES], m_y1[PASSES], m_x0[PASSES], m_x1[PASSES], m_c[PASSES];
+  bool m_y0[PASSES], m_y1[PASSES], m_x0[PASSES], m_x1[PASSES], m_c[PASSES], m_t[PASSES];
   __amdgpu_buffer_rsrc_t rsp, rsg, rsg1;
   bool lsec[PASSES];
   constexpr bool mixed = MIXED;
@@ -164,8 +177,9 @@ __device__ __forceinline__ void wgrad_mfma_body(const WParams& p, const int bid)
     rsg1 = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(reinterpret_cast<const char*>(p.C1 ? p.gath1 : p.gath0) - (int64_t)kpad * (Wl + 1) * p.C1 * ESZ), 0,
         0x7ffffff0, 0x00020000);
-    const bool rows_in_line = Ws >= BKP;          // a step stays inside one image row
-    const int q = rows_in_line ? 1 : BKP / Ws;    // image rows per step otherwise
+    const bool rows_in_line = !SMALL && Ws >= BKP;   // a step stays inside one image row
+    const int q = rows_in_line ? 1 : BKP / Ws;       // image rows per step otherwise
+    const int tail_rows = p.Msmall - (p.steps - 1) * BKP;   // SMALL: pixels of the last step (1 .. BKP)
 #pragma unroll
     for (int k = 0; k < PASSES; ++k) {
       const int v = k % NV;
@@ -197,6 +211,12 @@ __device__ __forceinline__ void wgrad_mfma_body(const WParams& p, const int bid)
       m_x1[k] = has_pad && rows_in_line && (kx[v] == klast) && (r == BKP - 1);
       m_c[k] = !col_ok[v] ||
                (has_pad && !rows_in_line && (((kx[v] == 0) && jx == 0) || ((kx[v] == klast) && jx == Ws - 1)));
+      m_t[k] = false;
+      if constexpr (SMALL) {
+        const int ir = a & (Hs - 1);              // image row of this lane's pixel, in every step
+        m_c[k] = m_c[k] || (ky[v] == 0 && ir == 0) || (ky[v] == klast && ir == Hs - 1);
+        m_t[k] = r >= tail_rows;
+      }
     }
   }
 
@@ -215,13 +235,16 @@ __device__ __forceinline__ void wgrad_mfma_body(const WParams& p, const int bid)
       const int gpix = s1 ? m0 : 4 * m0 - 2 * sj;
       const int gsoff = gpix * Cs_u * ESZ;
       const int gsoff1 = gpix * p.C1 * ESZ;
+      const bool last = SMALL && s == p.steps - 1;
 #pragma unroll
       for (int k = 0; k < PASSES; ++k) {
         // k4: plain bit operations -- with the short-circuit form the compiler threads the scalar tests into copies of
         // every request (12 more requests, ~250 instructions, 3-6 % slower k4 launches); S1 keeps the form it was tuned with
-        const bool inval = S1 ? (m_c[k] || (top && m_y0[k]) || (bot && m_y1[k]) || (left && m_x0[k]) || (right && m_x1[k]))
-                              : (m_c[k] | (top & m_y0[k]) | (bot & m_y1[k]) | (left & m_x0[k]) | (right & m_x1[k]));
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsp, (lptr_t)(pdst + k * (RPP * ROWB)), 16, pvoff[k], psoff, 0, 0);
+        const bool inval = SMALL ? (m_c[k] | (last & m_t[k]))
+                           : S1  ? (m_c[k] || (top && m_y0[k]) || (bot && m_y1[k]) || (left && m_x0[k]) || (right && m_x1[k]))
+                                 : (m_c[k] | (top & m_y0[k]) | (bot & m_y1[k]) | (left & m_x0[k]) | (right & m_x1[k]));
+        const unsigned pv = (SMALL && (last & m_t[k])) ? OOB : pvoff[k];
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsp, (lptr_t)(pdst + k * (RPP * ROWB)), 16, pv, psoff, 0, 0);
         const unsigned gv = inval ? OOB : gvoff[k];
         if constexpr (MIXED) {
           // LDS-DMA lands at M0 base + lane * 16 for ACTIVE lanes only, so the two masked halves compose
@@ -407,6 +430,30 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_batch_kernel(WBatch b) {
   wgrad_mfma_body<T, FAST, false, false, false>(b.p[k], (int)blockIdx.x - b.first[k]);
 }
 
+// The same launch for batchable problems of EITHER class (adn_wgrad_multi): a workgroup picks its problem, then the
+// addressing form the host chose for it.  first[k] is a multiple of 8 (the XCD-contiguous numbering inside a problem
+// relies on blockIdx & 7), so a problem may be followed by up to 7 idle workgroups.
+enum WForm : int { kFormGeneral = 0, kFormFast = 1, kFormSmall = 2 };
+struct WMulti {
+  WParams p[kWgradBatchMax];
+  int first[kWgradBatchMax + 1];
+  int form[kWgradBatchMax];
+  int n;
+};
+template <typename T>
+__global__ __launch_bounds__(256, 2) void wgrad_mfma_multi_kernel(WMulti b) {
+  int k = 0;
+#pragma unroll
+  for (int j = 1; j < kWgradBatchMax; ++j)
+    if (j < b.n && (int)blockIdx.x >= b.first[j]) k = j;
+  const int bid = (int)blockIdx.x - b.first[k];
+  if (bid >= b.p[k].tiles_r * b.p[k].tiles_c) return;
+  const int form = b.form[k];
+  if (form == kFormFast) wgrad_mfma_body<T, true, false, false, false>(b.p[k], bid);
+  else if (form == kFormSmall) wgrad_mfma_body<T, true, false, false, false, true>(b.p[k], bid);
+  else wgrad_mfma_body<T, false, false, false, false>(b.p[k], bid);
+}
+
 // generic path: one thread per (output element, split)
 template <typename T>
 __global__ __launch_bounds__(256) void wgrad_direct_kernel(WParams p, int pix_per_split) {
@@ -487,6 +534,7 @@ struct WPlan {
   bool mfma;
   bool fast;
   bool mixed;    // S1 only: fast path whose 128-column tiles straddle the two gathered sources
+  bool small;    // k4 bf16 only: the fast form's conditions with images of FEWER than bkp pixels (adn_wgrad_multi runs it)
   int nsplit, steps, tiles_r, tiles_c, pix_per_split;
   int64_t out_elems, slab_bytes;
 };
@@ -511,6 +559,7 @@ void make_wplan(const AdnWgradDesc* d, WPlan* pl) {
   pl->mfma = aligned;
   pl->fast = false;
   pl->mixed = false;
+  pl->small = false;
   if (aligned) {
     const int bkp = d->dtype == ADN_BF16 ? 64 : 32;
     const int maxC = d->C0 > d->C1 ? d->C0 : d->C1, maxR = d->R0 > d->R1 ? d->R0 : d->R1;
@@ -523,8 +572,11 @@ void make_wplan(const AdnWgradDesc* d, WPlan* pl) {
     } else {
       // no MIXED form: a two-source concat is fast only when every column tile lies inside one source; the offset test
       // counts 4 bytes per element for both dtypes and the 2x grid of the gathered tensor
-      pl->fast = pl->fast && (d->C1 == 0 || (d->C0 % 128 == 0 && C % 128 == 0)) &&
-                 msmall * 4 * maxC * 4 < (1ll << 31) && msmall * maxR * 4 < (1ll << 31);
+      const bool k4_src = (d->C1 == 0 || (d->C0 % 128 == 0 && C % 128 == 0)) &&
+                          msmall * 4 * maxC * 4 < (1ll << 31) && msmall * maxR * 4 < (1ll << 31);
+      pl->fast = pl->fast && k4_src;
+      pl->small = d->dtype == ADN_BF16 && pow2(d->Hs) && pow2(d->Ws) && d->Hs * d->Ws < bkp &&
+                  (d->R1 == 0 || d->R0 % 128 == 0) && k4_src;
     }
     pl->steps = (int)adn_cdiv(msmall, bkp);
     pl->tiles_r = (int)adn_cdiv(R, 128);
@@ -784,6 +836,56 @@ extern "C" int adn_wgrad_batch(const AdnWgradDesc* descs, int32_t n, void* strea
     ADN_SET_LDS_ONCE(lds, &wgrad_mfma_batch_kernel<uint16_t, false>);
     hipLaunchKernelGGL((wgrad_mfma_batch_kernel<uint16_t, false>), dim3((unsigned)b.first[n]), dim3(256), lds, st, b);
   }
+  ADN_CHECK_LAUNCH();
+  return ADN_OK;
+}
+
+// Batchable problems of either class in ONE launch, longest first: the workgroups of the 8x8-image layers (32 pixel
+// steps) start at once and the short ones (8, 2, 1 steps) fill the slots they leave, instead of a half-empty second round
+// of the long ones beside nothing and four rounds of short ones in a launch of their own.  Per problem the form is the
+// fast one (class 2), the small-image fast one (class 1 with a power-of-two image under the same source conditions) or
+// the general one.  The small-image form stages the same LDS tiles as the general one step for step, so dW and the norm
+// partials equal adn_wgrad_batch's bit for bit, with one exception: at 1x1 images the column tiles of the 12 taps that
+// can never be in range are written as +0.0f (partial 0.0) without being multiplied, so a NON-FINITE gradient no
+// longer turns those taps into NaN.  dW is still written completely.  Partials as adn_wgrad_batch_sq_count.
+extern "C" int adn_wgrad_multi(const AdnWgradDesc* descs, int32_t n, void* stream) {
+  ADN_CHECK_ARG(descs && n >= 1 && n <= kWgradBatchMax, "adn_wgrad_multi: 1 .. %d problems (got %d)", kWgradBatchMax, n);
+  WPlan pl[kWgradBatchMax];
+  int form[kWgradBatchMax], order[kWgradBatchMax];
+  for (int k = 0; k < n; ++k) {
+    const int32_t c = adn_wgrad_batchable(descs + k);
+    ADN_CHECK_ARG(c != 0, "adn_wgrad_multi: problem %d is not batchable (adn_wgrad_batchable)", k);
+    make_wplan(descs + k, &pl[k]);
+    pl[k].nsplit = 1;
+    form[k] = c == 2 ? kFormFast : (pl[k].small ? kFormSmall : kFormGeneral);
+    // insertion sort: pixel steps descending, then workgroups descending, then the caller's order
+    int at = k;
+    for (; at > 0; --at) {
+      const WPlan& o = pl[order[at - 1]];
+      const int to = o.tiles_r * o.tiles_c, tk = pl[k].tiles_r * pl[k].tiles_c;
+      if (o.steps > pl[k].steps || (o.steps == pl[k].steps && to >= tk)) break;
+      order[at] = order[at - 1];
+    }
+    order[at] = k;
+  }
+  WMulti b;
+  b.n = n;
+  b.first[0] = 0;
+  for (int s = 0; s < n; ++s) {
+    const int k = order[s];
+    fill_wparams(descs + k, pl[k], b.p[s]);
+    b.form[s] = form[k];
+    b.first[s + 1] = b.first[s] + (pl[k].tiles_r * pl[k].tiles_c + 7) / 8 * 8;
+  }
+  for (int s = n; s < kWgradBatchMax; ++s) {
+    b.p[s] = b.p[0];
+    b.form[s] = b.form[0];
+    b.first[s + 1] = b.first[n];
+  }
+  constexpr int lds = wgrad_lds<uint16_t>();
+  ADN_SET_LDS_ONCE(lds, &wgrad_mfma_multi_kernel<uint16_t>);
+  hipLaunchKernelGGL((wgrad_mfma_multi_kernel<uint16_t>), dim3((unsigned)b.first[n]), dim3(256), lds,
+                     reinterpret_cast<hipStream_t>(stream), b);
   ADN_CHECK_LAUNCH();
   return ADN_OK;
 }

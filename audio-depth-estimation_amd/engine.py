@@ -178,14 +178,14 @@ class UNetEngine(FlatParamEngine):
                 w6 = K.thin_wgrad_workspace_bytes(B, hs, wsz, 1, 64, 64)
             ws_bytes = max(ws_bytes, w1, w2, w3, w4, w5, w6)
             lv.update(P_d=pd, P_u=pu, P_gu=pgu, P_gd=pgd)
-            # small-image levels: their weight gradients ride in one multi-problem launch (adn_wgrad_batch)
+            # small-image levels: their weight gradients ride in one multi-problem launch (adn_wgrad_multi)
             # patch-staged levels: candidates for the shared-split launch (see _patch_groups below)
             if batching_patch and not edge0:
                 if cd_in_p == cd_in and K.wgrad_patch_batch_workspace_bytes(T, B, [(hs, wsz, cd_out, 0, cd_in_p, 0)]) >= 0:
                     pshape_d[i] = (hs, wsz, cd_out, 0, cd_in_p, 0)
                 if cu_out_p == cu_out and K.wgrad_patch_batch_workspace_bytes(T, B, [(hs, wsz, c_up0, c_up1, cu_out_p, 0)]) >= 0:
                     pshape_u[i] = (hs, wsz, c_up0, c_up1, cu_out_p, 0)
-            # (class of the problem -- a launch holds one class -- and its number of norm partials; 0 = own launch)
+            # (class of the problem -- 0 = own launch, else it rides in the multi-problem launch -- and its norm partials)
             batching = T == torch.bfloat16 and not os.environ.get('ADN_NO_WGRAD_BATCH')
             lv['wb_d'], lv['wbq_d'] = (K.wgrad_batchable(T, B, hs, wsz, cd_out, 0, cd_in_p, 0)
                                        if batching and not edge0 and cd_in_p == cd_in else (0, 0))
@@ -443,17 +443,16 @@ class UNetEngine(FlatParamEngine):
         # ---- up layers, outermost first
         # (weight gradients of the small-image levels are collected and launched together: nothing inside backward reads
         #  them, and their operands stay untouched until the end of the pass)
-        batch = {1: [], 2: []}            # per problem class (kernels.wgrad_batchable)
+        batch = []                        # problems of either class (kernels.wgrad_multi)
         held_u, held_d = [], []           # patch-staged groups (see _prepare: pb_u / pb_d)
         # (the reducer's gradient-ready hook wants every dW as early as possible: the same problems then go out as
-        #  one-problem launches of the same kernel form -- unsplit --, so both modes produce identical bits)
+        #  one-problem launches of the same entry point -- same kernel form, unsplit --, so both modes produce identical bits)
         use_batch = self.on_grad_ready is None
 
-        def flush(cls=None):
-            for c in ((cls,) if cls else (1, 2)):
-                if batch[c]:
-                    K.wgrad_batch(T, B, batch[c])
-                    del batch[c][:]
+        def flush():
+            if batch:
+                K.wgrad_multi(T, B, batch)
+                del batch[:]
         for i in range(n):
             lv = L[i]
             hs, wsz = lv['hs'], lv['ws']
@@ -483,12 +482,12 @@ class UNetEngine(FlatParamEngine):
                     K.wgrad_patch_batch(T, B, held_u, ws)
                     self._ready(lv['up'].weight)
             elif lv['wb_u']:
-                if len(batch[lv['wb_u']]) == 8:
-                    flush(lv['wb_u'])
-                batch[lv['wb_u']].append((hs, wsz, in0, in1, dz, None, self._flat_slice(self.flat_g, lv['up'].weight),
-                                          lv['up_sq'] if fused_norm else None))
+                if len(batch) == 8:
+                    flush()
+                batch.append((hs, wsz, in0, in1, dz, None, self._flat_slice(self.flat_g, lv['up'].weight),
+                              lv['up_sq'] if fused_norm else None))
                 if not use_batch:
-                    flush(lv['wb_u'])
+                    flush()
             else:
                 K.wgrad(T, B, hs, wsz, in0, in1, dz, None, self._flat_slice(self.flat_g, lv['up'].weight), ws,
                         c_valid=lv['cu_out'] if (i == 0 and self.cout_pad != lv['cu_out']) else 0,
@@ -517,13 +516,12 @@ class UNetEngine(FlatParamEngine):
                 if i == self.pb_d[0]:                     # the group's last (outermost) level
                     K.wgrad_patch_batch(T, B, held_d, ws)
             elif lv['wb_d']:
-                if len(batch[lv['wb_d']]) == 8:
-                    flush(lv['wb_d'])
-                batch[lv['wb_d']].append((hs, wsz, lv['Gd'], None, src, None,
-                                          self._flat_slice(self.flat_g, lv['down'].weight),
-                                          lv['down_sq'] if fused_norm else None))
+                if len(batch) == 8:
+                    flush()
+                batch.append((hs, wsz, lv['Gd'], None, src, None, self._flat_slice(self.flat_g, lv['down'].weight),
+                              lv['down_sq'] if fused_norm else None))
                 if not use_batch:
-                    flush(lv['wb_d'])
+                    flush()
             else:
                 flush()                                   # back at the wide levels: the collected small ones go first
                 K.wgrad(T, B, hs, wsz, lv['Gd'], None, src, None, self._flat_slice(self.flat_g, lv['down'].weight), ws,

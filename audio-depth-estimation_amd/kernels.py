@@ -180,8 +180,9 @@ def wgrad_batchable(dtype, B, Hs, Ws, R0, R1, C0, C1, c_valid=0):
     return int(lib.adn_wgrad_batchable(C.byref(d))), int(lib.adn_wgrad_batch_sq_count(C.byref(d)))
 
 
-def wgrad_batch(dtype, B, problems):
-    """problems: list of (Hs, Ws, plain0, plain1, gath0, gath1, dw, sq): up to 8 weight gradients in one launch."""
+def wgrad_batch(dtype, B, problems, entry='adn_wgrad_batch'):
+    """problems: list of (Hs, Ws, plain0, plain1, gath0, gath1, dw, sq): up to 8 weight gradients of ONE class in one
+    launch."""
     arr = (AdnWgradDesc * len(problems))()
     flops = 0.0
     for slot, (Hs, Ws, p0, p1, g0, g1, dw, sq) in zip(arr, problems):
@@ -190,10 +191,16 @@ def wgrad_batch(dtype, B, problems):
         C.memmove(C.byref(slot), C.byref(d), C.sizeof(AdnWgradDesc))
         flops += 2.0 * B * Hs * Ws * (d.R0 + d.R1) * 16 * (d.C0 + d.C1)
     ev = _prof_begin()
-    _lib.call('adn_wgrad_batch', arr, len(problems), _stream())
+    _lib.call(entry, arr, len(problems), _stream())
     _lib.annotate(label='wgrad', flops=flops)
     if ev is not None:
         _prof_end(ev, 'wgrad', flops)
+
+
+def wgrad_multi(dtype, B, problems):
+    """As wgrad_batch for problems of either class (adn_wgrad_multi): longest problem first inside the launch, the
+    small-image levels in the small-image fast form, dead taps of 1x1 images stored as zeros."""
+    wgrad_batch(dtype, B, problems, entry='adn_wgrad_multi')
 
 
 def wgrad_patch_batch_workspace_bytes(dtype, B, shapes):

@@ -158,6 +158,13 @@ int adn_wgrad(const AdnWgradDesc* d, void* stream);
 int32_t adn_wgrad_batchable(const AdnWgradDesc* d);
 int32_t adn_wgrad_batch_sq_count(const AdnWgradDesc* d);
 int adn_wgrad_batch(const AdnWgradDesc* descs, int32_t n, void* stream);
+/* Up to 8 batchable problems of EITHER class in one launch, longest problem first whatever the caller's order.  Class 2
+ * runs as in adn_wgrad_batch; class 1 with power-of-two images (1x1 .. 4x4, 2x4, ...) under the source conditions of class 2
+ * runs a small-image form of the same addressing, anything else the general form.  dW and the norm partials
+ * (adn_wgrad_batch_sq_count per problem) are bit-identical to adn_wgrad_batch's, except that at 1x1 images the 12 taps
+ * that can never be in range are stored as +0.0f without being multiplied: a non-finite operand no longer turns them
+ * into NaN.  Every dW is written completely. */
+int adn_wgrad_multi(const AdnWgradDesc* descs, int32_t n, void* stream);
 /* 2 .. 4 PATCH-STAGED weight gradients (the levels with >= 16 x 16 images: L1-L3, D1-D3 of unet_256) in ONE launch, each
  * with 1/n of the pixel splits of a lone launch: the f32 slabs of a launch are (workgroups x 128 KB) whatever the layer,
  * so n layers sharing the workgroups write and re-read 1/n of the slab bytes each.  Slabs back to back in

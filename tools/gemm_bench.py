@@ -92,6 +92,8 @@ def main():
     ap.add_argument('--b', type=int, default=0, help='batch for --mx8 (default 8)')
     ap.add_argument('--deep', action='store_true', help='the small-M split-K layers of unet_256 instead')
     ap.add_argument('--edge', action='store_true', help='thin outermost layers of unet_256 with their real epilogues')
+    ap.add_argument('--wgrad-small', action='store_true',
+                    help='the eight small-level weight gradients: two one-class launches against one adn_wgrad_multi launch')
     args = ap.parse_args()
     torch.manual_seed(0)
     if args.cold:
@@ -104,6 +106,8 @@ def main():
         return attn_main(args)
     if args.edge:
         return edge_main(args)
+    if args.wgrad_small:
+        return wgrad_small_main(args)
     for name, geom, Hs, C0, C1, N in (DEEP if args.deep else IGEMM):
         if args.only and args.only not in name:
             continue
@@ -141,6 +145,41 @@ def main():
         t = timeit(fn, args.iters)
         fl = 2.0 * B * Hs * Hs * (R0 + R1) * 16 * C
         print(f'{name:10s} M={B*Hs*Hs:7d} R={R0+R1:4d} C={C:4d}        {t*1e6:8.1f} us  {fl/t/1e12:7.1f} TF/s (incl. slab sum)', flush=True)
+
+
+# the weight gradients of the levels with <= 8 x 8 images in the order backward() meets them: name, Hs, R0, R1, C
+WGRAD_SMALL = [('D4', 8, 512, 512, 512), ('D5', 4, 512, 512, 512), ('D6', 2, 512, 512, 512), ('D7', 1, 512, 0, 512),
+               ('L7', 1, 512, 0, 512), ('L6', 2, 512, 0, 512), ('L5', 4, 512, 0, 512), ('L4', 8, 512, 0, 512)]
+
+
+def wgrad_small_main(args):
+    """Two launches of one class each (adn_wgrad_batch: fast form / general form) against adn_wgrad_multi, whole and in
+    parts: the parts price the small-image form (+ dead taps) and the merge into one launch separately."""
+    probs = {}
+    for name, Hs, R0, R1, C in WGRAD_SMALL:
+        p0 = torch.randn(B, Hs, Hs, R0, device=DEV).to(T)
+        p1 = torch.randn(B, Hs, Hs, R1, device=DEV).to(T) if R1 else None
+        g = torch.randn(B, 2 * Hs, 2 * Hs, C, device=DEV).to(T)
+        nsq = K.wgrad_batchable(T, B, Hs, Hs, R0, R1, C, 0)[1]
+        probs[name] = (Hs, Hs, p0, p1, g, None, torch.empty((R0 + R1) * 16 * C, device=DEV),
+                       torch.empty(nsq, dtype=torch.float64, device=DEV))
+    pick = lambda names: [probs[n] for n in names.split()]
+    big, small, mid = pick('D4 L4'), pick('D5 D6 D7 L7 L6 L5'), pick('D5 D6 L6 L5')
+    rows = [
+        ('batch: 8x8 levels (fast form)', lambda: K.wgrad_batch(T, B, big)),
+        ('batch: six levels <= 4x4 (general form)', lambda: K.wgrad_batch(T, B, small)),
+        ('batch: both launches', lambda: (K.wgrad_batch(T, B, big), K.wgrad_batch(T, B, small))),
+        ('multi: 8x8 levels alone', lambda: K.wgrad_multi(T, B, big)),
+        ('batch: 4x4 and 2x2 levels (general form)', lambda: K.wgrad_batch(T, B, mid)),
+        ('multi: 4x4 and 2x2 levels (small-image form)', lambda: K.wgrad_multi(T, B, mid)),
+        ('multi: six levels <= 4x4 (small-image form, dead taps)', lambda: K.wgrad_multi(T, B, small)),
+        ('multi: two launches, 8x8 then the six', lambda: (K.wgrad_multi(T, B, big), K.wgrad_multi(T, B, small))),
+        ('multi: all eight in one launch', lambda: K.wgrad_multi(T, B, list(probs.values()))),
+    ]
+    for what, fn in rows:
+        if args.only and args.only not in what:
+            continue
+        print(f'{what:58s} {timeit(fn, args.iters)*1e6:8.1f} us', flush=True)
 
 
 def edge_main(args):
