@@ -104,6 +104,17 @@ class AdnDualRegLoss(C.Structure):
     ]
 
 
+class AdnHybridLoss(C.Structure):
+    _fields_ = [
+        ('logits', c_void_p), ('dtype', c_int32), ('nb', c_int32), ('ld', c_int32), ('reg_mode', c_int32),
+        ('pixels', c_int64), ('pixels_global', c_int64),
+        ('centers', c_void_p), ('coarse', c_void_p), ('offset', c_void_p), ('bins', c_void_p), ('gt', c_void_p),
+        ('ce_weight', c_float), ('reg_weight', c_float), ('offset_reg_weight', c_float), ('label_smoothing', c_float),
+        ('final_depth', c_void_p), ('dlogits', c_void_p), ('doffset', c_void_p),
+        ('workspace', c_void_p), ('workspace_bytes', c_int64),
+    ]
+
+
 # name -> (restype, argtypes).  Must list every symbol include/adn.h declares
 # (tests/test_abi.py cross-checks this table against the header and the built library).
 _PROTOS = {
@@ -271,6 +282,10 @@ _PROTOS = {
     'adn_dualreg_loss': (C.c_int, [C.POINTER(AdnDualRegLoss), c_void_p]),
     'adn_dualreg_loss_finish': (C.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_float, c_float, c_float,
                                           c_void_p, c_void_p]),
+    'adn_hybrid_loss_workspace_bytes': (c_int64, [c_int64]),
+    'adn_hybrid_loss': (C.c_int, [C.POINTER(AdnHybridLoss), c_void_p]),
+    'adn_hybrid_loss_finish': (C.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_float, c_float, c_float, c_void_p,
+                                         c_void_p]),
 }
 
 _lib = None

@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import AdnAttnDesc, AdnCoarseLoss, AdnDistillSmall, AdnDualRegLoss  # noqa: E402
+from ._lib import AdnAttnDesc, AdnCoarseLoss, AdnDistillSmall, AdnDualRegLoss, AdnHybridLoss  # noqa: E402
 from ._lib import (ADN_BF16, ADN_F32, EPI_ACT, EPI_ADD, EPI_BWD, EPI_FINAL, EPI_RAW, EPI_Z_STATS, GEMM_S1, GEMM_S2, GEMM_T2,
                    AdnEpiSeg, AdnIgemmDesc, AdnMx8ConvDesc, AdnWgradDesc, ptr)
 
@@ -1145,3 +1145,51 @@ def dualreg_loss_finish(workspace, pixels, sums, n_valid, pixels_global, coarse_
     _dev(workspace, sums, n_valid, terms)
     _lib.call('adn_dualreg_loss_finish', ptr(workspace), int(pixels), ptr(sums), ptr(n_valid), int(pixels_global),
               float(coarse_weight), float(final_weight), float(offset_reg_weight), ptr(terms), _stream())
+
+
+# ---- hybrid coarse-depth family (csrc/hybrid.hip) -------------------------------------------------------------------
+REG_MODES = {'l1': 0, 'l2': 1}
+
+
+def hybrid_loss_workspace_bytes(pixels):
+    return _lib.load().adn_hybrid_loss_workspace_bytes(pixels)
+
+
+def hybrid_loss(logits, nb, centers, coarse, offset, bins, gt, final, dlogits, doffset, workspace, pixels_global=None,
+                ce_weight=1.0, reg_weight=1.0, offset_reg_weight=0.1, label_smoothing=0.0, reg_mode=0):
+    """logits [..., ld] (bf16 / f32, ld >= nb), centers f32 [nb], coarse / offset / gt f32 [pixels], bins int32 [pixels] ->
+    final = coarse + offset, dlogits (the logits' dtype and shape), doffset f32 [pixels] and the per-block partials in
+    ``workspace``; see adn_hybrid_loss."""
+    ld = logits.shape[-1]
+    pixels = logits.numel() // ld
+    _dev(logits, centers, coarse, offset, bins, gt, final, dlogits, doffset, workspace)
+    for name, t, dt in (('centers', centers, torch.float32), ('coarse', coarse, torch.float32),
+                        ('offset', offset, torch.float32), ('bins', bins, torch.int32), ('gt', gt, torch.float32),
+                        ('final', final, torch.float32), ('doffset', doffset, torch.float32),
+                        ('dlogits', dlogits, logits.dtype)):
+        if t is not None and (t.dtype != dt or not t.is_contiguous()):
+            raise RuntimeError(f'hybrid_loss: {name} must be contiguous {dt}')
+    for name, t in (('coarse', coarse), ('offset', offset), ('bins', bins), ('gt', gt), ('final', final),
+                    ('doffset', doffset)):
+        if t is not None and t.numel() != pixels:
+            raise RuntimeError(f'hybrid_loss: {name} has {t.numel()} elements for {pixels} pixels')
+    if ((centers is not None and centers.numel() != nb) or not logits.is_contiguous() or
+            (dlogits is not None and dlogits.shape != logits.shape)):
+        raise RuntimeError('hybrid_loss: centers must hold n_bins values; logits / dlogits contiguous and same shape')
+    d = AdnHybridLoss()
+    d.logits, d.dtype, d.nb, d.ld, d.reg_mode = ptr(logits), dtype_code(logits.dtype), nb, ld, int(reg_mode)
+    d.pixels, d.pixels_global = pixels, int(pixels_global if pixels_global is not None else pixels)
+    d.centers, d.coarse, d.offset, d.bins, d.gt = ptr(centers), ptr(coarse), ptr(offset), ptr(bins), ptr(gt)
+    d.ce_weight, d.reg_weight, d.offset_reg_weight = float(ce_weight), float(reg_weight), float(offset_reg_weight)
+    d.label_smoothing = float(label_smoothing)
+    d.final_depth, d.dlogits, d.doffset = ptr(final), ptr(dlogits), ptr(doffset)
+    d.workspace, d.workspace_bytes = ptr(workspace), (_nbytes(workspace) if workspace is not None else 0)
+    _lib.call('adn_hybrid_loss', C.byref(d), _stream())
+
+
+def hybrid_loss_finish(workspace, pixels, sums, pixels_global, ce_weight, reg_weight, offset_reg_weight, terms):
+    """workspace None: sums f64[4] are taken as given (all-reduced); terms f32[5] = ce, regression, offset_reg, coarse_l1,
+    total (or None)."""
+    _dev(workspace, sums, terms)
+    _lib.call('adn_hybrid_loss_finish', ptr(workspace), int(pixels), ptr(sums), int(pixels_global), float(ce_weight),
+              float(reg_weight), float(offset_reg_weight), ptr(terms), _stream())

@@ -9,9 +9,10 @@ rgb_depth_model's, so the state_dict keys differ and the classes cannot be share
 ``forward(x) -> (logits [B, n_bins, H, W], depth [B, 1, H, W])`` runs as an op tape on libadn (coarse_engine.py); the
 fused coarse_engine.CoarseDepthTrainer is the fast path, the loss modules below serve the reference-style autograd loop
 and ``CoarseDepthTrainer.from_criterion``.  ``DualRegressionModel`` / ``DualRegressionLoss`` (reference :857-1056, model_type
-'dual_reg' of the script) are constructed directly, as the reference does; they run on dualreg_engine.py.  Functional gaps
-raise NotImplementedError: model_type 'lite' / 'hybrid' (and 'dual_reg' through the factory), ``bilinear=False``, and an
-input size different from ``output_size`` (the bilinear resize of the logits / offset features; train_coarse_depth.py
+'dual_reg' of the script) are constructed directly, as the reference does; they run on dualreg_engine.py.
+``CoarseWithOffsetModel`` / ``CoarseOffsetLoss`` (reference :591-850, model_type 'hybrid') are constructed directly too and
+run on hybrid_engine.py.  Functional gaps raise NotImplementedError: model_type 'lite' (and 'hybrid' / 'dual_reg' through
+the factory), ``bilinear=False``, and an input size different from ``output_size`` (the bilinear resize of the logits / offset features; train_coarse_depth.py
 always feeds images_size inputs).  ``2 <= n_bins <= 512``; back-propagating through the returned ``depth`` in the autograd
 loop additionally needs ``n_bins <= 256`` (adn_bins_bwd), the fused trainer does not.
 """
@@ -257,6 +258,137 @@ class DualRegressionLoss(nn.Module):
         return total_loss, {'total': total_loss, 'coarse': coarse_loss, 'final': final_loss, 'offset_reg': offset_reg}
 
 
+class CoarseWithOffsetModel(nn.Module):
+    """Hybrid model (reference :591-770): a shared encoder, a classification decoder + 1x1 class head whose softmax
+    expectation over ``bin_centers`` is the coarse depth, and an offset decoder whose features are fused with the DETACHED
+    coarse depth ([64 + 1] -> 64 -> 32 channels, biased 3x3 convs in front of BatchNorm) before the 1x1 offset head.
+    ``forward(x) -> (logits [B, n_bins, H, W], coarse_depth, offset, final_depth)``, f32, final = coarse + offset.
+    Constructed directly (the reference's factory does not build it, train_coarse_depth.py:290-296);
+    ``torch.manual_seed(s)`` before the constructor gives the reference's weights.  ``plane_channels``: width of the NHWC
+    record that carries the coarse depth into the fusion conv (None: the engine's default, see
+    dualreg_engine.DualRegEngine).  ``2 <= n_bins <= 512``; back-propagating through the returned depths in the autograd
+    loop additionally needs ``n_bins <= 256`` (adn_bins_bwd), the fused trainer does not."""
+
+    def __init__(self, input_channels: int = 2, n_bins: int = 8, base_channels: int = 64, output_size: int = 256,
+                 bilinear: bool = True):
+        super().__init__()
+        if not bilinear:
+            raise NotImplementedError('CoarseWithOffsetModel(bilinear=False) is not implemented (no reference caller builds it)')
+        self.n_bins = n_bins
+        self.output_size = output_size
+        self.input_channels = input_channels
+        self.base_channels = base_channels
+        factor = 2 if bilinear else 1
+        self.inc = DoubleConv(input_channels, base_channels)
+        self.down1 = Down(base_channels, base_channels * 2)
+        self.down2 = Down(base_channels * 2, base_channels * 4)
+        self.down3 = Down(base_channels * 4, base_channels * 8)
+        self.down4 = Down(base_channels * 8, base_channels * 16 // factor)
+        self.coarse_up1 = Up(base_channels * 16, base_channels * 8 // factor, bilinear)
+        self.coarse_up2 = Up(base_channels * 8, base_channels * 4 // factor, bilinear)
+        self.coarse_up3 = Up(base_channels * 4, base_channels * 2 // factor, bilinear)
+        self.coarse_up4 = Up(base_channels * 2, base_channels, bilinear)
+        self.coarse_head = nn.Conv2d(base_channels, n_bins, kernel_size=1)
+        self.offset_up1 = Up(base_channels * 16, base_channels * 8 // factor, bilinear)
+        self.offset_up2 = Up(base_channels * 8, base_channels * 4 // factor, bilinear)
+        self.offset_up3 = Up(base_channels * 4, base_channels * 2 // factor, bilinear)
+        self.offset_up4 = Up(base_channels * 2, base_channels, bilinear)
+        self.offset_fusion = nn.Sequential(
+            nn.Conv2d(base_channels + 1, base_channels, 3, padding=1),
+            nn.BatchNorm2d(base_channels),
+            nn.ReLU(inplace=True),
+            nn.Conv2d(base_channels, base_channels // 2, 3, padding=1),
+            nn.BatchNorm2d(base_channels // 2),
+            nn.ReLU(inplace=True),
+        )
+        self.offset_head = nn.Conv2d(base_channels // 2, 1, kernel_size=1)
+        self.register_buffer('bin_centers', torch.linspace(0, 1, n_bins))
+        self._init_weights()
+        self._engine = None
+        self.compute_dtype = default_compute_dtype()
+        self.plane_channels = None
+
+    def _init_weights(self):
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+
+    def set_bin_centers(self, bin_centers: torch.Tensor):
+        """Set bin centers for depth reconstruction (in place when the shape allows: a captured step reads the buffer)."""
+        if bin_centers.shape == self.bin_centers.shape:
+            self.bin_centers.copy_(bin_centers.detach())
+        else:
+            self.bin_centers = bin_centers.to(self.bin_centers.device)
+
+    def engine(self):
+        from ..hybrid_engine import HybridEngine
+        e = self._engine
+        if e is None or e.requested_dtype != self.compute_dtype or e.requested_plane != self.plane_channels:
+            object.__setattr__(self, '_engine', HybridEngine(self, self.compute_dtype, self.plane_channels))
+        return self._engine
+
+    def forward(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """x [B, C, S, S] -> (logits, coarse_depth, offset, final_depth).  In training mode under autograd all four hang
+        off one autograd node, so the reference's ``criterion(*model(x), gt, bins)[0].backward()`` loop works."""
+        from ..hybrid_engine import run_hybrid
+        return run_hybrid(self.engine(), x, self.training)
+
+    def predict_depth(self, x: torch.Tensor) -> torch.Tensor:
+        return self.forward(x)[3]
+
+    def get_num_params(self) -> int:
+        return sum(p.numel() for p in self.parameters() if p.requires_grad)
+
+    def get_component_params(self) -> Dict:
+        """Parameter count of each component (reference :750-770)."""
+        count = lambda mods: sum(p.numel() for m in mods for p in m.parameters() if p.requires_grad)
+        return {
+            'encoder': count([self.inc, self.down1, self.down2, self.down3, self.down4]),
+            'coarse_decoder': count([self.coarse_up1, self.coarse_up2, self.coarse_up3, self.coarse_up4, self.coarse_head]),
+            'offset_decoder': count([self.offset_up1, self.offset_up2, self.offset_up3, self.offset_up4,
+                                     self.offset_fusion, self.offset_head]),
+            'total': self.get_num_params(),
+        }
+
+
+class CoarseOffsetLoss(nn.Module):
+    """Label-smoothed cross-entropy of the class logits + L1 / L2 of the final depth + mean |offset|, all over every
+    pixel (no valid mask), and |coarse - gt| for monitoring (reference :773-850).  Plain torch;
+    hybrid_engine.HybridTrainer.from_criterion reads ``fused_spec()``."""
+
+    def __init__(self, ce_weight: float = 1.0, regression_weight: float = 1.0, offset_reg_weight: float = 0.1,
+                 regression_loss: str = 'l1', label_smoothing: float = 0.0):
+        super().__init__()
+        self.ce_weight = ce_weight
+        self.regression_weight = regression_weight
+        self.offset_reg_weight = offset_reg_weight
+        self.ce_loss = nn.CrossEntropyLoss(label_smoothing=label_smoothing)
+        self.regression_loss_type = regression_loss
+
+    def fused_spec(self):
+        """(ce_weight, regression_weight, offset_reg_weight, reg_mode, label_smoothing) as adn_hybrid_loss takes them;
+        every regression_loss other than 'l1' is the reference's mse branch."""
+        return (float(self.ce_weight), float(self.regression_weight), float(self.offset_reg_weight),
+                'l1' if self.regression_loss_type == 'l1' else 'l2', float(self.ce_loss.label_smoothing))
+
+    def forward(self, logits: torch.Tensor, coarse_depth: torch.Tensor, offset: torch.Tensor, final_depth: torch.Tensor,
+                target_depth: torch.Tensor, target_bins: torch.Tensor) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+        ce_loss = self.ce_loss(logits, target_bins)
+        if self.regression_loss_type == 'l1':
+            reg_loss = F.l1_loss(final_depth, target_depth)
+        else:
+            reg_loss = F.mse_loss(final_depth, target_depth)
+        offset_reg = offset.abs().mean()
+        total_loss = self.ce_weight * ce_loss + self.regression_weight * reg_loss + self.offset_reg_weight * offset_reg
+        return total_loss, {'total': total_loss, 'ce': ce_loss, 'regression': reg_loss, 'offset_reg': offset_reg,
+                            'coarse_l1': F.l1_loss(coarse_depth, target_depth)}
+
+
 # ---- loss modules (reference :294-468); plain torch on whatever device their inputs live on ---------------------------
 class OrdinalRegressionLoss(nn.Module):
     """Ordinal regression loss (reference :294-321; no caller uses it)."""
@@ -380,7 +512,8 @@ def init_net(net, init_type='kaiming', init_gain=0.02, gpu_ids=[]):
 
 _UNBUILT = {
     'lite': "model_type 'lite' (CoarseDepthLite: k4 s2 conv / transposed-conv stack with biases) is not implemented",
-    'hybrid': "model_type 'hybrid' (CoarseWithOffsetModel: second decoder + offset head) is not implemented",
+    'hybrid': "model_type 'hybrid' is not built by this factory (nor by the reference's): construct "
+              "CoarseWithOffsetModel directly, as train_coarse_depth does",
     'dual_reg': "model_type 'dual_reg' is not built by this factory (nor by the reference's): construct "
                 "DualRegressionModel directly, as train_coarse_depth does",
 }

@@ -437,17 +437,21 @@ def warm_restart_lr(epoch, base_lr, T_0=20, T_mult=2, eta_min=1e-6):
 
 
 def main_coarse(argv=None):
-    """The reference's train_coarse_depth.py:133-645 for model_type 'unet' and 'dual_reg'.  'unet': CoarseDepthUNet,
-    CoarseDepthLoss (soft CE, or focal with --use_focal) with valid = depth > 0, targets binned on the device.  'dual_reg':
-    DualRegressionModel constructed directly (:282-288), DualRegressionLoss(--coarse_weight, --final_weight,
-    --offset_reg_weight), no bin centres on the model, validation on the final depth.  Both: AdamW(wd 0.01) / Adam /
+    """The reference's train_coarse_depth.py:133-645 for model_type 'unet', 'hybrid' and 'dual_reg'.  'unet':
+    CoarseDepthUNet, CoarseDepthLoss (soft CE, or focal with --use_focal) with valid = depth > 0, targets binned on the
+    device.  'hybrid': CoarseWithOffsetModel constructed directly (:293-301), CoarseOffsetLoss(--ce_weight,
+    --regression_weight, --offset_reg_weight, 'l1', label_smoothing=0.1) over every pixel (:336-343), targets binned on the
+    device, validation on the final depth.  'dual_reg': DualRegressionModel constructed directly (:282-288),
+    DualRegressionLoss(--coarse_weight, --final_weight, --offset_reg_weight), no bin centres on the model, validation on
+    the final depth.  All: AdamW(wd 0.01) / Adam /
     SGD(momentum 0.9), clip_grad_norm_(1.0), CosineAnnealingWarmRestarts(20, 2, 1e-6) per epoch; checkpoints
     ./checkpoints/<experiment>/checkpoint_N.pth and best.pth with {epoch, state_dict, optimizer, bin_centers, bin_edges}."""
     from .coarse_engine import CoarseDepthTrainer
     from .dataloader.utils_dataset import compute_bins
     from .dualreg_engine import DualRegressionTrainer
-    from .models.coarse_depth_model import (CoarseDepthLoss, DualRegressionLoss, DualRegressionModel,
-                                            define_coarse_depth_model)
+    from .hybrid_engine import HybridTrainer
+    from .models.coarse_depth_model import (CoarseDepthLoss, CoarseOffsetLoss, CoarseWithOffsetModel, DualRegressionLoss,
+                                            DualRegressionModel, define_coarse_depth_model)
     p = argparse.ArgumentParser(description='Train Coarse Depth Classification Model (MI355X)')
     p.add_argument('--dataset', type=str, default='batvisionv2', choices=['batvisionv1', 'batvisionv2'])
     p.add_argument('--sparse_method', type=str, default='downup_015')
@@ -489,9 +493,11 @@ def main_coarse(argv=None):
     args.device, args.num_workers, args.seed = 'cuda', 0, 42
     dev = _device(args, local if world > 1 else None)
     say = print if rank == 0 else (lambda *a, **k: None)
-    dual = args.model_type == 'dual_reg'
+    dual, hybrid = args.model_type == 'dual_reg', args.model_type == 'hybrid'
     if dual:                # the reference's factory does not know it either: constructed directly (:282-288)
         model = DualRegressionModel(input_channels=2, base_channels=args.base_channels, output_size=S)
+    elif hybrid:            # likewise (:293-301)
+        model = CoarseWithOffsetModel(input_channels=2, n_bins=args.n_bins, base_channels=args.base_channels, output_size=S)
     else:
         model = define_coarse_depth_model(model_type=args.model_type, input_channels=2, n_bins=args.n_bins,
                                           base_channels=args.base_channels, output_size=S)
@@ -514,6 +520,14 @@ def main_coarse(argv=None):
         step = lambda audio, gt: trainer.step(audio, gt / norm)
         predict = lambda mm, b: mm.engine().forward_net(b[0], False)[2] * norm
         line = lambda m: f'total={m[3]:.4f}, coarse={m[0]:.4f}, final={m[1]:.4f}, off={m[2]:.4f}'
+    elif hybrid:
+        say('  - Hybrid model (CE + offset)')
+        criterion = CoarseOffsetLoss(ce_weight=args.ce_weight, regression_weight=args.regression_weight,
+                                     offset_reg_weight=args.offset_reg_weight, regression_loss='l1', label_smoothing=0.1)
+        trainer = HybridTrainer.from_criterion(eng, criterion, **opt_kw)
+        step = lambda audio, gt: trainer.step(audio, None, gt / norm, edges=dev_edges)
+        predict = lambda mm, b: mm.engine().forward_net(b[0], False)[3] * norm
+        line = lambda m: f'total={m[4]:.4f}, ce={m[0]:.4f}, reg={m[1]:.4f}, off={m[2]:.4f}'
     else:
         criterion = CoarseDepthLoss(n_bins=args.n_bins, ce_weight=args.ce_weight, regression_weight=args.regression_weight,
                                     use_focal=args.use_focal, use_soft_ce=not args.use_focal,
@@ -549,7 +563,7 @@ def main_coarse(argv=None):
             audio, gt = _to_device(batch, dev, fe)
             _, terms = step(audio, gt)
             acc.append(terms.detach().clone())
-        m = torch.stack(acc).mean(0).tolist() if acc else [float('nan')] * 4
+        m = torch.stack(acc).mean(0).tolist() if acc else [float('nan')] * 5
         say(f'Epoch {epoch}: {line(m)}, time={time.time() - t0:.1f}s')
         state = {'epoch': epoch, 'state_dict': model.state_dict(), 'optimizer': trainer.state_dict(),
                  'bin_centers': centers, 'bin_edges': edges}

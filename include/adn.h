@@ -728,6 +728,46 @@ int adn_dualreg_loss_finish(const void* workspace, int64_t pixels, double* sums,
                             int64_t pixels_global, float coarse_weight, float final_weight, float offset_reg_weight,
                             float* terms, void* stream);
 
+/* Hybrid coarse-depth family (CoarseWithOffsetModel / CoarseOffsetLoss, models/coarse_depth_model.py): the loss tail
+ * behind the class head and the offset head.  f32 arithmetic, f64 final reductions, no atomics, bit-reproducible.
+ *
+ * adn_hybrid_loss: ONE pass over the class logits [pixels][ld] (dtype, nb <= ld, 2 <= nb <= 512).  Every operand is
+ * required.  coarse is the softmax expectation that the forward-only adn_coarse_loss pass wrote before the offset branch
+ * ran; it is taken as given, so final_depth = coarse + offset (one f32 add, always written) agrees bit for bit with the
+ * plane the offset branch saw.  No valid mask anywhere (the reference has none); P = pixels_global.  Per pixel, with
+ * p = softmax(x), d_k = x_k - max, logZ = log sum exp d, t = bins, eps = label_smoothing, e = final - gt:
+ *   ce      = (1 - eps) (logZ - d_t) + eps (logZ - (sum_k d_k) / nb)        nn.CrossEntropyLoss(label_smoothing=eps)
+ *   reg     = |e| (reg_mode 0, L1)  or  e^2 (reg_mode 1, L2)
+ *   r       = reg_weight sgn(e) / P (L1)  or  reg_weight 2 e / P (L2),  sgn(0) = 0
+ *   dlogits_k = ce_weight / P (p_k - (1 - eps) [k == t] - eps / nb) + r p_k (centers[k] - coarse)     columns [nb, ld) = 0
+ *   doffset = r + offset_reg_weight sgn(offset) / P
+ * i.e. the gradient of ce_weight mean(ce) + reg_weight mean(reg) + offset_reg_weight mean|offset| (the coarse depth is
+ * NOT detached in final).  Per-block f64 partials of sum ce, sum reg, sum |offset|, sum |coarse - gt| (monitoring) go
+ * into the workspace. */
+typedef struct {
+  const void* logits;
+  int32_t dtype, nb, ld, reg_mode;   /* reg_mode: 0 = L1, 1 = L2 */
+  int64_t pixels, pixels_global;     /* pixels_global: pixel count of the global batch under data parallelism */
+  const float* centers;              /* [nb] */
+  const float* coarse;               /* [pixels] */
+  const float* offset;               /* [pixels] */
+  const int32_t* bins;               /* [pixels] */
+  const float* gt;                   /* [pixels] */
+  float ce_weight, reg_weight, offset_reg_weight, label_smoothing;
+  float* final_depth;                /* [pixels] */
+  void* dlogits;                     /* [pixels][ld], dtype */
+  float* doffset;                    /* [pixels] */
+  void* workspace;
+  int64_t workspace_bytes;
+} AdnHybridLoss;
+int64_t adn_hybrid_loss_workspace_bytes(int64_t pixels);
+int adn_hybrid_loss(const AdnHybridLoss* d, void* stream);
+/* workspace != NULL: reduce the partials adn_hybrid_loss left for `pixels` pixels into sums f64[4]; NULL: take sums as
+ * given (all-reduced by the caller).  terms != NULL: terms f32[5] = (ce, regression, offset_reg, coarse_l1, total), each
+ * its sum / pixels_global, total = ce_weight ce + reg_weight regression + offset_reg_weight offset_reg. */
+int adn_hybrid_loss_finish(const void* workspace, int64_t pixels, double* sums, int64_t pixels_global, float ce_weight,
+                           float reg_weight, float offset_reg_weight, float* terms, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
