@@ -238,6 +238,9 @@ _PROTOS = {
     'adn_l0_forward': (C.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p,
                                  c_void_p]),
     'adn_d0_dgrad_num_partials': (c_int64, [c_int32, c_int32, c_int32]),
+    'adn_l0_forward_stats_num_partials': (c_int64, [c_int32, c_int32, c_int32]),
+    'adn_l0_forward_stats': (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                       c_void_p, c_void_p]),
     'adn_d0_dgrad': (C.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, C.POINTER(AdnEpiSeg), C.POINTER(AdnEpiSeg),
                                c_void_p]),
     'adn_thin_wgrad_workspace_bytes': (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),

@@ -20,21 +20,25 @@ from ._lib import EPI_ACT, EPI_ADD, GEMM_S1
 
 
 class ConvLinear(Op):
-    """Conv2d 1x1 with bias, no norm / activation (the class head, adabins_distillation_model.py:192)."""
+    """Conv2d 1x1 (the class head, adabins_distillation_model.py:192) or 3x3 / padding 1 (CoarseDepthLite's head,
+    coarse_depth_model.py:263) with bias, no norm / activation."""
 
     def __init__(self, src, conv, out):
         self.src, self.conv, self.out = src, conv, out
+        self.ks = conv.kernel_size[0]
+        assert conv.kernel_size in ((1, 1), (3, 3)) and conv.stride == (1, 1) and conv.padding == (self.ks // 2,) * 2
         out.producer = self
         src.consumers.append(self)
 
     def prepare(self, eng):
         T, dev, B = eng.dtype, eng.dev, eng.B
         s, o = self.src, self.out
-        self.w_fwd = torch.empty(o.C, K.s1_row_stride(T, 1, s.C), dtype=T, device=dev)
-        self.w_dg = torch.empty(s.C, K.s1_row_stride(T, 1, o.C), dtype=T, device=dev) if s.needs_grad else None
-        q = lambda n, segs, cin: K.igemm_query(T, GEMM_S1, B, o.H, o.W, cin, 0, n, segs, ks=1)[1]
+        ks, taps = self.ks, self.ks * self.ks
+        self.w_fwd = torch.empty(o.C, K.s1_row_stride(T, taps, s.C), dtype=T, device=dev)
+        self.w_dg = torch.empty(s.C, K.s1_row_stride(T, taps, o.C), dtype=T, device=dev) if s.needs_grad else None
+        q = lambda n, segs, cin: K.igemm_query(T, GEMM_S1, B, o.H, o.W, cin, 0, n, segs, ks=ks)[1]
         self._ws = max(q(o.C, [o.C], s.C), q(s.C, [s.C], o.C) if s.needs_grad else 0,
-                       K.wgrad_workspace_bytes(T, B, o.H, o.W, o.C, 0, s.C, 0, ks=1),
+                       K.wgrad_workspace_bytes(T, B, o.H, o.W, o.C, 0, s.C, 0, ks=ks),
                        K.channel_sum_workspace_bytes(B * o.H * o.W, o.C))
 
     def workspace_bytes(self, eng):
@@ -42,22 +46,23 @@ class ConvLinear(Op):
 
     def pack(self, eng):
         master = eng._flat_slice(eng.flat_p, self.conv.weight)
-        K.pack_rows(master, self.out.C, 1, self.src.C, self.w_fwd)
+        taps = self.ks * self.ks
+        K.pack_rows(master, self.out.C, taps, self.src.C, self.w_fwd)
         if self.w_dg is not None:
-            K.pack_transpose_taps(master, self.out.C, 1, self.src.C, self.w_dg, flip=False)
+            K.pack_transpose_taps(master, self.out.C, taps, self.src.C, self.w_dg, flip=taps > 1)
 
     def fwd(self, eng, training):
         o = self.out
         K.igemm(eng.dtype, GEMM_S1, eng.B, o.H, o.W, self.src.data, None, self.w_fwd, o.C, EPI_ACT,
-                [K.Seg(o.C, out0=o.data, bias=self.conv.bias, slope=1.0)], eng.workspace, ks=1)
+                [K.Seg(o.C, out0=o.data, bias=self.conv.bias, slope=1.0)], eng.workspace, ks=self.ks)
 
     def bwd(self, eng):
         o, s = self.out, self.src
         fg = lambda p: eng._flat_slice(eng.flat_g, p)
-        K.wgrad(eng.dtype, eng.B, o.H, o.W, o.grad, None, s.data, None, fg(self.conv.weight), eng.workspace, ks=1)
+        K.wgrad(eng.dtype, eng.B, o.H, o.W, o.grad, None, s.data, None, fg(self.conv.weight), eng.workspace, ks=self.ks)
         K.channel_sum(o.grad, eng.B * o.H * o.W, o.C, o.C, fg(self.conv.bias), eng.workspace)
         K.igemm(eng.dtype, GEMM_S1, eng.B, o.H, o.W, o.grad, None, self.w_dg, s.C, EPI_ADD,
-                [K.Seg(s.C, out0=s.grad, accumulate=s.written)], eng.workspace, ks=1)
+                [K.Seg(s.C, out0=s.grad, accumulate=s.written)], eng.workspace, ks=self.ks)
         s.written = True
 
 

@@ -6,6 +6,8 @@ dc_engine.py, the class head is adabins_engine.ConvLinear, and everything behind
 adn_coarse_loss (csrc/coarse.hip): softmax expectation, classification loss (soft CE / focal / CE), masked L1 of the
 expectation and the gradient of their weighted sum, written once in the logits' dtype.  The logits [B,H,W,n_bins] stay
 NHWC in the compute dtype and are only expanded to f32 NCHW when a caller asks for them (forward()).
+CoarseLiteEngine runs CoarseDepthLite (:199-287) through the same engine: only the tape in front of the logits differs
+(the ``_build_tape`` hook).
 """
 from __future__ import annotations
 
@@ -13,35 +15,21 @@ import torch
 
 from . import kernels as K
 from .adabins_engine import ConvLinear
-from .dc_engine import Act, DCEngine, flag_solo, mark_tail_writers
+from .dc_engine import Act, ConvK4BNAct, ConvS2BNLeaky, ConvT2BNReLU, DCEngine, flag_solo, mark_tail_writers
 from .trainer import OptimTail
 
 
 class CoarseDepthEngine(DCEngine):
+    name = 'CoarseDepthUNet'
+    head_attr = 'outc'               # the model's attribute that holds the class-head conv
+
     def __init__(self, module, compute_dtype=torch.bfloat16):
-        super().__init__(module, None, compute_dtype, 'CoarseDepthUNet')
+        super().__init__(module, None, compute_dtype, self.name)
         self.autograd_pass = 0
 
-    def _prepare_net(self, x):
-        if not self._bound():
-            self.bind_parameters()
-        B, Cin, H, W = x.shape
-        key = (B, Cin, H, W, x.device)
-        if self._shape_enter(key):
-            return
+    def _build_tape(self, Cin, H, W):
+        """-> (inputs, ops, feature record in front of the class head): the tape hook of _prepare_net."""
         m = self.module
-        if Cin != m.input_channels:
-            raise RuntimeError(f'expected input[{B}, {Cin}, {H}, {W}] to have {m.input_channels} channels, but got {Cin} '
-                               'channels instead')
-        if W != m.output_size:
-            raise NotImplementedError(f'CoarseDepthUNet: input width {W} != output_size {m.output_size}: the bilinear resize '
-                                      f'of the {m.n_bins}-channel logits (coarse_depth_model.py:159-161) is not implemented')
-        if not 2 <= m.n_bins <= 512:
-            raise NotImplementedError(f'CoarseDepthUNet: n_bins={m.n_bins} is outside the range [2, 512] of adn_coarse_loss')
-        self.B, self.dev = B, x.device
-        self._scratch = {}
-        self.epc = 8 if self.dtype == torch.bfloat16 else 4
-        self.pairs = []
         inp = self.thin_input('x', Cin, H, W)
         ops, f = m.inc.adn_ops([inp], 'x1', H, W)
         feats = [f]
@@ -53,10 +41,39 @@ class CoarseDepthEngine(DCEngine):
         for i, up in enumerate((m.up1, m.up2, m.up3, m.up4)):
             o, d = up.adn_ops(d, feats[3 - i], f'd{4 - i}')
             ops += o
+        return [(inp, 0, Cin)], ops, d
+
+    def check_input(self, shape):
+        """The shape refusals of forward, on the host (no device work)."""
+        B, Cin, H, W = shape
+        m = self.module
+        if Cin != m.input_channels:
+            raise RuntimeError(f'expected input[{B}, {Cin}, {H}, {W}] to have {m.input_channels} channels, but got {Cin} '
+                               'channels instead')
+        if W != m.output_size:
+            raise NotImplementedError(f'{self.name}: input width {W} != output_size {m.output_size}: the bilinear resize '
+                                      f'of the {m.n_bins}-channel logits (coarse_depth_model.py:159-161) is not implemented')
+        if not 2 <= m.n_bins <= 512:
+            raise NotImplementedError(f'{self.name}: n_bins={m.n_bins} is outside the range [2, 512] of adn_coarse_loss')
+
+    def _prepare_net(self, x):
+        if not self._bound():
+            self.bind_parameters()
+        B, Cin, H, W = x.shape
+        key = (B, Cin, H, W, x.device)
+        if self._shape_enter(key):
+            return
+        m = self.module
+        self.check_input((B, Cin, H, W))
+        self.B, self.dev = B, x.device
+        self._scratch = {}
+        self.epc = 8 if self.dtype == torch.bfloat16 else 4
+        self.pairs = []
+        self.inputs, ops, d = self._build_tape(Cin, H, W)
         self.logits = Act('logits', m.n_bins, H, W)
-        self.class_op = ConvLinear(d, m.outc, self.logits)
+        self.class_op = ConvLinear(d, getattr(m, self.head_attr), self.logits)
         ops.append(self.class_op)
-        self.inputs, self.ops = [(inp, 0, Cin)], ops
+        self.ops = ops
         acts = {}
         for op in ops:
             for a in list(getattr(op, 'srcs', [])) + [getattr(op, 'src', None), getattr(op, 'out', None)]:
@@ -87,7 +104,7 @@ class CoarseDepthEngine(DCEngine):
         (the fused trainer): the softmax expectation is left to the caller's own adn_coarse_loss pass, which writes
         ``depth`` together with the loss and the gradient, so the logits are read once per step."""
         if not x.is_cuda:
-            raise RuntimeError('CoarseDepthUNet needs a HIP device tensor (libadn has no CPU path)')
+            raise RuntimeError(f'{self.name} needs a HIP device tensor (libadn has no CPU path)')
         x = x.contiguous().float()
         self._prepare_net(x)
         if self.weights_dirty or self._packed_version != self._version_sum():
@@ -127,13 +144,57 @@ class CoarseDepthEngine(DCEngine):
             a.written = False
         self._final = set(id(p) for p, _, _ in self.param_meta if not p.requires_grad)
         self._wm = len(self.param_meta)
-        outc = self.module.outc
+        outc = getattr(self.module, self.head_attr)
         for op in reversed(self.ops):
             if op.out.needs_grad:
                 op.bwd(self)
                 if op is self.class_op:
                     self._mark(outc.bias)
                     self._ready(outc.weight)
+
+
+class CoarseLiteEngine(CoarseDepthEngine):
+    """CoarseDepthLite (reference coarse_depth_model.py:199-287): five ConvS2BNLeaky, five ConvT2BNReLU, no skips, and the
+    biased 3x3 class head (ConvLinear); everything behind the logits is CoarseDepthEngine's.  The first layer of the
+    bf16 / base-64 network reads the f32 NCHW input itself (adn_l0_forward_stats / adn_thin_wgrad, ``thin_l0``)."""
+    name = 'CoarseDepthLite'
+    head_attr = 'head'
+
+    def __init__(self, module, compute_dtype=torch.bfloat16):
+        if compute_dtype == torch.float8_e4m3fn:
+            raise NotImplementedError('CoarseDepthLite: the MX-fp8 path covers the 3x3 DoubleConv layers only (mxfp8 has no '
+                                      'k4 stride-2 kernels)')
+        super().__init__(module, compute_dtype)
+
+    def check_input(self, shape):
+        super().check_input(shape)
+        H, W = shape[2], shape[3]
+        if H % 32 or W % 32:
+            raise RuntimeError(f'CoarseDepthLite: input {H}x{W} is not divisible by 32 (five stride-2 levels)')
+
+    def _build_tape(self, Cin, H, W):
+        m = self.module
+        enc, dec = m.encoder, m.decoder
+        self.thin_l0 = ConvK4BNAct.thin_ok(self, enc[0], W)
+        inp = self.thin_input('x', Cin, H, W)
+        if self.thin_l0:            # nothing reads the padded NHWC copy of the input: neither allocated nor written
+            inp.data = torch.empty(0, dtype=self.dtype, device=self.dev)
+        ops, src, h, w = [], inp, H, W
+        for i in range(0, len(enc), 3):
+            h, w = h // 2, w // 2
+            out = Act(f'e{i // 3}', enc[i].out_channels, h, w)
+            ops.append(ConvS2BNLeaky(src, enc[i], enc[i + 1], out, slope=enc[i + 2].negative_slope))
+            src = out
+        for i in range(0, len(dec), 3):
+            h, w = h * 2, w * 2
+            out = Act(f'd{i // 3}', dec[i].out_channels, h, w)
+            ops.append(ConvT2BNReLU(src, dec[i], dec[i + 1], out))
+            src = out
+        return ([] if self.thin_l0 else [(inp, 0, Cin)]), ops, src
+
+    def load_input(self, x):
+        self.x_in = x
+        super().load_input(x)
 
 
 class _CoarseFunction(torch.autograd.Function):
@@ -153,7 +214,7 @@ class _CoarseFunction(torch.autograd.Function):
     def backward(ctx, g_logits, g_depth):
         eng = ctx.engine
         if ctx.stamp != eng.autograd_pass:
-            raise RuntimeError('CoarseDepthUNet: backward through a forward whose activations were overwritten by a later '
+            raise RuntimeError(f'{eng.name}: backward through a forward whose activations were overwritten by a later '
                                'training forward of the same module')
         lg, nb = eng.logits, eng.module.n_bins
         if g_depth is not None:

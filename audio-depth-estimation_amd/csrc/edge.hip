@@ -5,6 +5,8 @@
 // 16 pixels, everything else is about moving whole 64-byte / 128-byte pieces of NHWC rows once.
 //
 //   l0_fwd        out[b,oy,ox,:64]  = leaky / relu ( sum_{ky,kx,ci} x[b,ci,2oy-1+ky,2ox-1+kx] * w[o][ky][kx][ci] )
+//   l0_fwd_stats  z[b,oy,ox,:64]    = the same sum + bias, and BatchNorm statistics (sum z, sum z^2): the first layer of
+//                 CoarseDepthLite, which has a BatchNorm behind it (models/coarse_depth_model.py:218-219)
 //   d0_dgrad      G[b,i,j,c]        = mask * sum_{ky,kx} dz[b,2i-1+ky,2j-1+kx] * w[c][ky][kx]      c in skip(64) ++ up(64)
 //                 + BatchNorm-backward statistics of the up half (sum g, sum g*xhat)
 //   thin_wgrad    dW[c][tap*CT+ct]  = sum_{b,i,j} plain[b,i,j,c] * thin[b,ct,2i-1+ky,2j-1+kx]
@@ -156,6 +158,117 @@ __global__ __launch_bounds__(256) void l0_fwd_kernel(const float* __restrict__ x
       *reinterpret_cast<u32x4_t*>(out_relu + tile + 512) = p1;
     }
    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// First conv in front of a train-mode BatchNorm (CoarseDepthLite's encoder.0/1): z = conv(x) + bias as bf16
+// [B][Hs][Ws][64] and one partial row [2][64] per workgroup of sum z and sum z^2, taken from the f32 z BEFORE the bf16
+// rounding (the ADN_EPI_Z_STATS convention, epilogue.h).  Same work split, fragments and LDS-staged 1 KiB stores as
+// l0_fwd_kernel; the sums of a lane's 16 channels ride in registers over its pixels, then go lane row -> wave -> workgroup
+// in a fixed order (no atomics: bit-reproducible for a given shape).
+__global__ __launch_bounds__(256) void l0_fwd_stats_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                           const float* __restrict__ bias, int B, int Hs, int Ws,
+                                                           uint16_t* z_out, float* partials) {
+  __shared__ __attribute__((aligned(16))) char stage_all[4][2048];
+  __shared__ float red[4][2][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n = lane & 15, q = lane >> 4;
+  const int Hl = 2 * Hs, Wl = 2 * Ws;
+  char* stage = stage_all[wave];
+  u32x4_t* st_w[2];
+  const u32x4_t* st_r[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    st_w[h] = reinterpret_cast<u32x4_t*>(stage + n * 128 + (((h * 4 + q) ^ ((n >> 1) & 7)) << 4));
+    const int pc = h * 64 + lane, px = pc >> 3;
+    st_r[h] = reinterpret_cast<const u32x4_t*>(stage + px * 128 + (((pc & 7) ^ ((px >> 1) & 7)) << 4));
+  }
+  bf16x8_t wf[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const float* wp = w + edge_ch(t, n) * 32 + q * 8;          // k = ky*8 + kx*2 + ci, this lane: ky = q
+    const f32x4_t lo = *reinterpret_cast<const f32x4_t*>(wp), hi = *reinterpret_cast<const f32x4_t*>(wp + 4);
+    const u32x4_t c = {pk_bf16(lo[0], lo[1]), pk_bf16(lo[2], lo[3]), pk_bf16(hi[0], hi[1]), pk_bf16(hi[2], hi[3])};
+    wf[t] = as_frag(c);
+  }
+  // this lane's 16 channels: h*32 + q*8 + e (the two 16-byte pieces of its pixel)
+  float bz[16], s1[16], s2[16];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    bz[e] = bias ? bias[(e >> 3) * 32 + q * 8 + (e & 7)] : 0.f;
+    s1[e] = s2[e] = 0.f;
+  }
+  const int gpr = Ws >> 4;
+  const int gu = (gpr & 3) == 0 ? 4 : 1;                     // groups per work unit (see l0_fwd_kernel)
+  const unsigned upr = (unsigned)(gpr / gu);
+  const unsigned units = (unsigned)B * Hs * upr;
+  for (unsigned u = blockIdx.x * 4 + wave; u < units; u += gridDim.x * 4) {
+    const unsigned bi = u / upr;
+    const int jg0 = (int)(u - bi * upr) * gu;
+    const int b = (int)(bi / (unsigned)Hs);
+    const int oy = (int)(bi - (unsigned)b * Hs);
+    for (int jg = jg0; jg < jg0 + gu; ++jg) {
+      const int ox = jg * 16 + n;
+      const int iy = 2 * oy - 1 + q;
+      const bool rok = (unsigned)iy < (unsigned)Hl;
+      const float* r0 = x + (((int64_t)b * 2) * Hl + (rok ? iy : 0)) * Wl;
+      const float* r1 = r0 + (int64_t)Hl * Wl;
+      float a0[4], a1[4];
+      window4(r0, rok, ox, Wl, a0);
+      window4(r1, rok, ox, Wl, a1);
+      u32x4_t bc;
+#pragma unroll
+      for (int kx = 0; kx < 4; ++kx) bc[kx] = pk_bf16(a0[kx], a1[kx]);
+      const bf16x8_t bfr = as_frag(bc);
+      f32x4_t acc[4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[t], bfr, f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+      const int64_t tile = (((int64_t)b * Hs + oy) * Ws + jg * 16) * 64 + lane * 8;      // this lane's first piece
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        float o[8];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          o[e] = acc[2 * h][e] + bz[h * 8 + e];
+          o[4 + e] = acc[2 * h + 1][e] + bz[h * 8 + 4 + e];
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          s1[h * 8 + e] += o[e];
+          s2[h * 8 + e] += o[e] * o[e];
+        }
+        *st_w[h] = Chunk<uint16_t>::pack(o);
+      }
+      asm volatile("" ::: "memory");
+      const u32x4_t p0 = *st_r[0], p1 = *st_r[1];
+      asm volatile("" ::: "memory");
+      *reinterpret_cast<u32x4_t*>(z_out + tile) = p0;
+      *reinterpret_cast<u32x4_t*>(z_out + tile + 512) = p1;
+    }
+  }
+  // the 16 pixels of a lane row, then the 4 waves: one partial row per workgroup (a workgroup without work writes zeros)
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) {
+      s1[e] += __shfl_xor(s1[e], o, 64);
+      s2[e] += __shfl_xor(s2[e], o, 64);
+    }
+  }
+  if (n == 0) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int c = (e >> 3) * 32 + q * 8 + (e & 7);
+      red[wave][0][c] = s1[e];
+      red[wave][1][c] = s2[e];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 128) {
+    const int st = threadIdx.x >> 6, c = threadIdx.x & 63;
+    partials[((int64_t)blockIdx.x * 2 + st) * 64 + c] = (red[0][st][c] + red[1][st][c]) + (red[2][st][c] + red[3][st][c]);
   }
 }
 
@@ -502,6 +615,32 @@ extern "C" int adn_l0_forward(const float* x, const float* w, int32_t B, int32_t
   const int64_t units = (int64_t)B * Hs * (Ws / 16) / ((Ws / 16) % 4 == 0 ? 4 : 1);
   hipLaunchKernelGGL(l0_fwd_kernel, dim3(edge_blocks(units * 2, kPixBlocks)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, w,
                      B, Hs, Ws, slope, reinterpret_cast<uint16_t*>(out_leaky), reinterpret_cast<uint16_t*>(out_relu));
+  ADN_CHECK_LAUNCH();
+  return ADN_OK;
+}
+
+namespace {
+inline int l0_stats_blocks(int32_t B, int32_t Hs, int32_t Ws) {
+  const int64_t units = (int64_t)B * Hs * (Ws / 16) / ((Ws / 16) % 4 == 0 ? 4 : 1);
+  return edge_blocks(units * 2, kPixBlocks);
+}
+}  // namespace
+
+extern "C" int64_t adn_l0_forward_stats_num_partials(int32_t B, int32_t Hs, int32_t Ws) {
+  if (B <= 0 || Hs <= 0 || Ws <= 0 || Ws % 16) return -1;
+  return l0_stats_blocks(B, Hs, Ws);
+}
+
+extern "C" int adn_l0_forward_stats(const float* x, const float* w, const float* bias, int32_t B, int32_t Hs, int32_t Ws,
+                                    int32_t cin, int32_t cout, void* z, float* partials, void* stream) {
+  ADN_CHECK_ARG(cin == 2 && cout == 64, "adn_l0_forward_stats: built for 2 -> 64 channels (got %d -> %d)", cin, cout);
+  ADN_CHECK_ARG(B > 0 && Hs > 0 && Ws > 0 && Ws % 16 == 0, "adn_l0_forward_stats: bad shape B=%d Hs=%d Ws=%d (Ws %% 16)", B,
+                Hs, Ws);
+  ADN_CHECK_ARG(x && w && z && partials, "adn_l0_forward_stats: null operand");
+  ADN_CHECK_ARG((int64_t)B * Hs * Ws * 4 * 64 < (1ll << 40) && (int64_t)B * Hs * Ws * 4 < (1ll << 31),
+                "adn_l0_forward_stats: tensor too large");
+  hipLaunchKernelGGL(l0_fwd_stats_kernel, dim3(l0_stats_blocks(B, Hs, Ws)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), x, w, bias, B, Hs, Ws, reinterpret_cast<uint16_t*>(z), partials);
   ADN_CHECK_LAUNCH();
   return ADN_OK;
 }

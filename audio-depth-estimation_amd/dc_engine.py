@@ -8,6 +8,8 @@ and in reverse for the backward pass.  Every op is a handful of libadn launches 
   ConvBNReLU   (Conv2d k3/k1 -> BatchNorm2d -> ReLU)   S1 implicit GEMM with the Z+stats epilogue, BN finalize,
                one BN+ReLU materialisation pass; backward = [ReLU+BN stats pass |fused into the consumer's dgrad
                epilogue] -> finalize -> apply -> wgrad -> dgrad (S1 GEMM with the flipped/transposed operand)
+  ConvS2BNLeaky / ConvT2BNReLU   (Conv2d / ConvTranspose2d k4 s2 p1 + bias -> BatchNorm2d -> LeakyReLU / ReLU, the layers
+               of CoarseDepthLite)   the same protocol on the k4 geometries S2 / T2 of adn_igemm (ConvK4BNAct)
   MaxPool2 / Upsample2x / Head1x1        memory-bound kernels of csrc/dcnet.hip
 
 Data layout in HBM: activations NHWC in the compute dtype (bf16 throughput path, f32 exact path); per
@@ -26,7 +28,7 @@ import torch
 from . import _lib
 from . import kernels as K
 from .flat import FlatParamEngine
-from ._lib import EPI_ACT, EPI_ADD, EPI_BWD, EPI_Z_STATS, GEMM_S1
+from ._lib import EPI_ACT, EPI_ADD, EPI_BWD, EPI_Z_STATS, GEMM_S1, GEMM_S2, GEMM_T2
 
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
@@ -44,7 +46,9 @@ class Act:
         self.consumers = []
         self.fused_bwd = False       # sole consumer is a conv: its dgrad epilogue applies the ReLU mask + BN stats
         self.written = False         # a consumer already wrote .grad in the current backward pass
+        self.slope = 0.0             # negative-side slope of the activation that produced .data (0: ReLU): the mask value
         self.z = self.mean = self.istd = self.bpart = None
+        self.scale = self.shift = None     # train-mode BN affine of the producer (ConvK4BNAct: handed to the consumer's EPI_BWD)
         self.bpart_rows = 0
         self.alias_of = None         # this record's gradient IS that record's gradient buffer (gated residual)
         self.pair_data = self.pair_grad = None      # [2B,...] buffers when stacked with a sibling ([left; right])
@@ -311,7 +315,7 @@ class ConvBNReLU(Op):
             tgt = s.target()
             if s.fused_bwd:
                 epi = EPI_BWD
-                segs.append(K.Seg(s.C, out0=s.grad, ref=s.data, slope=0.0, z=s.z, mean=s.mean, istd=s.istd,
+                segs.append(K.Seg(s.C, out0=s.grad, ref=s.data, slope=s.slope, z=s.z, mean=s.mean, istd=s.istd,
                                   partials=s.bpart, accumulate=tgt.written))
             else:
                 segs.append(K.Seg(s.C, out0=s.grad if s.needs_grad else eng.scratch_like(s), accumulate=tgt.written))
@@ -320,6 +324,196 @@ class ConvBNReLU(Op):
             K.conv3x3_mx8(B, o.H, o.W, self.g8, self.g8s, None, None, self.w8_dg, self.wsc_dg, self.c0 + self.c1, epi, segs)
         else:
             K.igemm(T, GEMM_S1, B, o.H, o.W, G, None, self.w_dg, self.c0 + self.c1, epi, segs, eng.workspace, ks=self.ks)
+
+
+class ConvK4BNAct(Op):
+    """The post-activation k4 / stride 2 / padding 1 layers of CoarseDepthLite (coarse_depth_model.py:217-260 of the
+    reference) on the k4 geometries of adn_igemm; see the two subclasses.  One source, one output, bias in front of BN.
+
+    The flat parameter storage of a 4-D weight is [dim0][kh][kw][dim1] = the master [X][16][Y] of adn_pack_weights: it IS
+    the S2 operand, adn_wgrad writes its gradient in exactly this layout, and the T2 operand [4][Y][4][X] is one pack.
+    conv:  X = Cout, Y = Cin;  forward S2 (master), input gradient T2 (pack)
+    convT: X = Cin,  Y = Cout; forward T2 (pack),   input gradient S2 (master)
+    The first layer of the bf16 / 64-channel network may run on the thin-input kernels of csrc/edge.hip (``thin``): the
+    conv + bias + BN statistics straight from the f32 NCHW network input (adn_l0_forward_stats), its weight gradient by
+    adn_thin_wgrad; ADN_LITE_L0_IGEMM=1 keeps it on adn_igemm over the zero-padded input record."""
+
+    transposed = False
+    slope = 0.0
+
+    def __init__(self, src, conv, bn, out):
+        assert conv.kernel_size == (4, 4) and conv.stride == (2, 2) and conv.padding == (1, 1)
+        assert conv.dilation == (1, 1) and conv.groups == 1 and getattr(conv, 'output_padding', (0, 0)) == (0, 0)
+        self.src, self.conv, self.bn, self.out = src, conv, bn, out
+        big, small = (out, src) if self.transposed else (src, out)
+        if (big.H, big.W) != (2 * small.H, 2 * small.W):
+            raise RuntimeError(f'k4 s2 p1 layer between {src.H}x{src.W} and {out.H}x{out.W}: the large grid must be twice '
+                               'the small one (odd sizes are not implemented)')
+        self.hs, self.ws = small.H, small.W
+        out.producer = self
+        out.slope = self.slope
+        src.consumers.append(self)
+
+    @staticmethod
+    def thin_ok(eng, conv, W):
+        """The thin first-layer route applies: bf16, 2 -> 64 channels, small-grid width a multiple of 32 (adn_thin_wgrad's
+        K-step)."""
+        return (eng.dtype == torch.bfloat16 and conv.in_channels == 2 and conv.out_channels == 64 and W % 2 == 0 and
+                (W // 2) % 32 == 0 and not os.environ.get('ADN_LITE_L0_IGEMM'))
+
+    def prepare(self, eng):
+        T, dev, B = eng.dtype, eng.dev, eng.B
+        s, o = self.src, self.out
+        hs, ws = self.hs, self.ws
+        N = self.N = o.C
+        w = self.conv.weight
+        X, Y = w.shape[0], w.shape[1]
+        self.cin_real = getattr(s, 'C_real', s.C)
+        assert (Y, X) == ((N, self.cin_real) if self.transposed else (self.cin_real, N))
+        self.thin = not self.transposed and not s.needs_grad and getattr(eng, 'thin_l0', False)
+        self.need_dgrad = s.needs_grad
+        self.c_valid = self.cin_real if self.cin_real != s.C else 0
+        assert not (self.transposed and self.c_valid)
+        f32 = dict(dtype=torch.float32, device=dev)
+        gf, gb = (GEMM_T2, GEMM_S2) if self.transposed else (GEMM_S2, GEMM_T2)
+        self.gf, self.gb = gf, gb
+        # operands: the parameter memory (f32) / its bf16 mirror is the S2 form; own buffers for the padded first layer
+        # and the T2 form
+        self.w_s2 = self.w_t2 = None
+        need_s2 = (not self.transposed and not self.thin) or (self.transposed and self.need_dgrad)
+        need_t2 = self.transposed or self.need_dgrad
+        self.s2_is_view = need_s2 and not self.c_valid
+        if self.s2_is_view:
+            src_flat = eng.flat_p if T == torch.float32 else eng.flat_w16
+            self.w_s2 = eng._flat_slice(src_flat, w).view(X, 16, Y)
+        elif need_s2:
+            self.w_s2 = torch.zeros(X, 16, s.C, dtype=T, device=dev)
+        if need_t2:
+            self.w_t2 = torch.empty(16 * X * Y, dtype=T, device=dev)
+        o.z = torch.empty_like(o.data)
+        o.mean, o.istd = torch.empty(N, **f32), torch.empty(N, **f32)
+        o.scale, o.shift = torch.empty(N, **f32), torch.empty(N, **f32)        # train-mode affine (read again by backward)
+        self.escale, self.eshift = torch.empty(N, **f32), torch.empty(N, **f32)    # eval-mode affine (+ folded bias)
+        self.coef = torch.empty(2 * N, **f32)
+        if self.thin:
+            self.P = K.l0_forward_stats_num_partials(B, hs, ws)
+            ws1 = K.thin_wgrad_workspace_bytes(B, hs, ws, 2, 64, 0)
+            ws3 = 0
+        else:
+            self.P, ws1 = K.igemm_query(T, gf, B, hs, ws, s.C, 0, N, [N], epi=EPI_Z_STATS)
+            ws1 = max(ws1, K.igemm_query(T, gf, B, hs, ws, s.C, 0, N, [N], epi=EPI_ACT)[1])
+            if self.transposed:
+                ws3 = K.wgrad_workspace_bytes(T, B, hs, ws, s.C, 0, N, 0)
+            else:
+                ws3 = K.wgrad_workspace_bytes(T, B, hs, ws, N, 0, s.C, 0, c_valid=self.c_valid)
+        self.part = torch.empty(self.P * 2 * N, **f32)
+        ws2 = 0
+        if self.need_dgrad:
+            # the source is itself the output of a k4 layer whose only consumer is this op (flag_solo): its mask and
+            # BatchNorm-backward sums ride in this op's input-gradient epilogue
+            assert s.fused_bwd, 'ConvK4BNAct: a source that needs a gradient must be the output of a ConvK4BNAct'
+            s.bpart_rows, ws2 = K.igemm_query(T, gb, B, hs, ws, N, 0, s.C, [s.C], epi=EPI_BWD)
+            s.bpart = torch.empty(s.bpart_rows * 2 * s.C, **f32)
+        if o.needs_grad and not o.fused_bwd:
+            if self.slope != 0.0:
+                raise NotImplementedError('a LeakyReLU record whose consumer is not a k4 conv has no stand-alone mask + '
+                                          'BN-statistics pass')
+            o.bpart_rows = K.relu_bwd_stats_num_partials(B * o.H * o.W, N)
+            o.bpart = torch.empty(o.bpart_rows * 2 * N, **f32)
+        self._ws = max(ws1, ws2, ws3)
+        need = K.BN_REDUCE_SLICES * 2 * N
+        if getattr(eng, 'bn_scratch', None) is None or eng.bn_scratch.numel() < need or eng.bn_scratch.device != dev:
+            eng.bn_scratch = torch.empty(max(need, K.BN_REDUCE_SLICES * 2 * 1024), **f32)
+
+    def workspace_bytes(self, eng):
+        return self._ws
+
+    def pack(self, eng):
+        w = self.conv.weight
+        X, Y = w.shape[0], w.shape[1]
+        master = eng._flat_slice(eng.flat_p, w)
+        s2_out = self.w_s2 if (self.w_s2 is not None and not self.s2_is_view) else None
+        if s2_out is not None or self.w_t2 is not None:
+            K.pack_weights(master, X, Y, eng.dtype, s2_out, self.w_t2, y_pad=self.src.C if s2_out is not None else None)
+
+    def _bn_track(self):
+        bn = self.bn
+        track = bn.track_running_stats and bn.running_mean is not None
+        return (bn.running_mean if track else None, bn.running_var if track else None,
+                bn.num_batches_tracked if track else None)
+
+    def fwd(self, eng, training):
+        T, B, s, o, bn, N = eng.dtype, eng.B, self.src, self.out, self.bn, self.N
+        hs, ws = self.hs, self.ws
+        pixels = B * o.H * o.W
+        w_f = self.w_t2 if self.transposed else self.w_s2
+        rmean, rvar, nbt = self._bn_track()
+        cbias = self.conv.bias
+        if self.thin:
+            wm = eng._flat_slice(eng.flat_p, self.conv.weight)
+            K.l0_forward_stats(eng.x_in, wm, cbias, B, hs, ws, o.z, self.part)
+        if training:
+            if not self.thin:
+                K.igemm(T, self.gf, B, hs, ws, s.data, None, w_f, N, EPI_Z_STATS,
+                        [K.Seg(N, out0=o.z, partials=self.part, bias=cbias)], eng.workspace, algo_c=self.cin_real)
+            K.bn_fwd_finalize(self.part, self.P, N, pixels, bn.weight, bn.bias, bn.eps,
+                              BN_MOMENTUM if bn.momentum is None else bn.momentum, rmean, rvar, nbt, o.mean, o.istd,
+                              o.scale, o.shift, scratch=eng.bn_scratch)
+            K.bn_act(o.z, pixels, N, o.scale, o.shift, self.slope, o.data, None)
+            return
+        K.bn_eval_affine(bn.weight, bn.bias, rmean, rvar, bn.eps, self.escale, self.eshift)
+        if self.thin:                                   # z already carries the bias
+            K.bn_act(o.z, pixels, N, self.escale, self.eshift, self.slope, o.data, None)
+            return
+        if cbias is not None:                           # BN(conv + b) = conv * scale + (shift + b * scale)
+            self.eshift.addcmul_(cbias.detach(), self.escale)
+        K.igemm(T, self.gf, B, hs, ws, s.data, None, w_f, N, EPI_ACT,
+                [K.Seg(N, out0=o.data, scale=self.escale, shift=self.eshift, slope=self.slope)], eng.workspace,
+                algo_c=self.cin_real)
+
+    def bwd(self, eng):
+        T, B, s, o, bn, N = eng.dtype, eng.B, self.src, self.out, self.bn, self.N
+        hs, ws = self.hs, self.ws
+        pixels = B * o.H * o.W
+        G = o.grad
+        if not o.fused_bwd:
+            K.relu_bwd_stats(G, o.data, o.z, o.mean, o.istd, pixels, N, o.bpart)
+        fg = lambda p: eng._flat_slice(eng.flat_g, p)
+        K.bn_bwd_finalize(o.bpart, o.bpart_rows, N, pixels, fg(bn.weight), fg(bn.bias), self.coef, scratch=eng.bn_scratch)
+        K.bn_bwd_apply(G, o.z, pixels, N, o.scale, o.mean, o.istd, self.coef)             # G is now d loss / d z
+        eng._mark(bn.weight, bn.bias)
+        if self.conv.bias is not None:
+            # a bias in front of BatchNorm has an identically zero gradient (BN subtracts the batch mean)
+            fg(self.conv.bias).zero_()
+            eng._mark(self.conv.bias)
+        dw = fg(self.conv.weight)
+        if self.thin:
+            K.thin_wgrad(eng.x_in, G, None, B, hs, ws, dw, eng.workspace)
+        elif self.transposed:                            # plain = layer input (small grid), gathered = dZ (large grid)
+            K.wgrad(T, B, hs, ws, s.data, None, G, None, dw, eng.workspace)
+        else:                                            # plain = dZ (small grid), gathered = layer input (large grid)
+            K.wgrad(T, B, hs, ws, G, None, s.data, None, dw, eng.workspace, c_valid=self.c_valid)
+        eng._ready(self.conv.weight)
+        if not self.need_dgrad:
+            return
+        w_b = self.w_s2 if self.transposed else self.w_t2
+        seg = K.Seg(s.C, out0=s.grad, ref=s.data, slope=s.slope, z=s.z, mean=s.mean, istd=s.istd, partials=s.bpart,
+                    scale=s.scale, shift=s.shift, accumulate=s.written)
+        s.written = True
+        K.igemm(T, self.gb, B, hs, ws, G, None, w_b, s.C, EPI_BWD, [seg], eng.workspace)
+
+
+class ConvS2BNLeaky(ConvK4BNAct):
+    """Conv2d(k4, s2, p1, bias) -> BatchNorm2d -> LeakyReLU(slope): ADN_GEMM_S2 forward, ADN_GEMM_T2 input gradient."""
+
+    def __init__(self, src, conv, bn, out, slope=0.2):
+        self.slope = float(slope)
+        super().__init__(src, conv, bn, out)
+
+
+class ConvT2BNReLU(ConvK4BNAct):
+    """ConvTranspose2d(k4, s2, p1, bias) -> BatchNorm2d -> ReLU: ADN_GEMM_T2 forward, ADN_GEMM_S2 input gradient."""
+    transposed = True
 
 
 class MaxPool2(Op):
@@ -658,6 +852,11 @@ def flag_solo(a):
     prod = a.producer
     if isinstance(prod, Upsample2x) and hasattr(prod.src, 'C_real') and a.data is None:
         a.C_real, a.C = prod.src.C_real, prod.src.C
+        return
+    if isinstance(prod, ConvK4BNAct):
+        # the k4 chain (CoarseDepthLite): every record has one consumer; when that is another k4 conv, its input-gradient
+        # epilogue applies the activation mask (with the record's slope) + BN statistics.  No channel padding here.
+        a.fused_bwd = a.needs_grad and len(a.consumers) == 1 and isinstance(a.consumers[0], ConvK4BNAct)
         return
     if not isinstance(prod, ConvBNReLU):
         return

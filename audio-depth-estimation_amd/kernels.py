@@ -120,6 +120,24 @@ def igemm_query(dtype, geom, B, Hs, Ws, C0, C1, N, seg_channels, ks=0, epi=EPI_R
     return p, wsb
 
 
+def igemm_describe(dtype, geom, B, Hs, Ws, C0, C1, N, seg_channels, ks=0, epi=EPI_RAW):
+    """The plan line of adn_igemm_describe for a shape ('ring bm=256 ...'; the first word is the kernel form), host only."""
+    d = AdnIgemmDesc()
+    d.ks = ks
+    d.dtype, d.geom, d.B, d.Hs, d.Ws, d.C0, d.C1, d.N = dtype_code(dtype), geom, B, Hs, Ws, C0, C1, N
+    d.in0 = d.w = 1
+    d.in1 = 1 if C1 else None
+    d.epi = epi
+    for i, c in enumerate(seg_channels[:2]):
+        d.seg[i].channels = c
+        d.seg[i].out0 = d.seg[i].ref = 1                # (dummy non-null operands: the query only validates and plans)
+    buf = C.create_string_buffer(256)
+    lib = _lib.load()
+    if lib.adn_igemm_describe(C.byref(d), buf, len(buf)) != 0:
+        raise RuntimeError('adn_igemm_describe failed: ' + lib.adn_last_error().decode())
+    return buf.value.decode()
+
+
 def igemm(dtype, geom, B, Hs, Ws, in0, in1, w, N, epi, segs, workspace=None, algo_c=None, ks=0):
     """algo_c: real (unpadded) gathered channel count, only used for the algorithmic FLOP count."""
     d = _igemm_desc(dtype, geom, B, Hs, Ws, in0, in1, w, N, epi, segs, workspace, ks)
@@ -489,6 +507,22 @@ def l0_forward(x, w_master, B, Hs, Ws, slope, out_leaky, out_relu):
     _dev(x, w_master, out_leaky, out_relu)
     _lib.call('adn_l0_forward', ptr(x), ptr(w_master), B, Hs, Ws, x.shape[1], w_master.numel() // (16 * x.shape[1]),
               float(slope), ptr(out_leaky), ptr(out_relu), _stream())
+    _lib.annotate(label='edge', flops=2.0 * B * Hs * Ws * 64 * 16 * x.shape[1])
+
+
+def l0_forward_stats_num_partials(B, Hs, Ws):
+    n = _lib.load().adn_l0_forward_stats_num_partials(B, Hs, Ws)
+    if n < 0:
+        raise RuntimeError(f'adn_l0_forward_stats: bad shape B={B} Hs={Hs} Ws={Ws} (Ws % 16)')
+    return n
+
+
+def l0_forward_stats(x, w_master, bias, B, Hs, Ws, z, partials):
+    """First conv (2 -> 64 channels) in front of a train-mode BatchNorm: z bf16 [B,Hs,Ws,64] = conv(x) + bias and
+    l0_forward_stats_num_partials rows [2][64] of sum z / sum z^2 (the EPI_Z_STATS convention)."""
+    _dev(x, w_master, bias, z, partials)
+    _lib.call('adn_l0_forward_stats', ptr(x), ptr(w_master), ptr(bias), B, Hs, Ws, x.shape[1],
+              w_master.numel() // (16 * x.shape[1]), ptr(z), ptr(partials), _stream())
     _lib.annotate(label='edge', flops=2.0 * B * Hs * Ws * 64 * 16 * x.shape[1])
 
 

@@ -11,8 +11,9 @@ fused coarse_engine.CoarseDepthTrainer is the fast path, the loss modules below 
 and ``CoarseDepthTrainer.from_criterion``.  ``DualRegressionModel`` / ``DualRegressionLoss`` (reference :857-1056, model_type
 'dual_reg' of the script) are constructed directly, as the reference does; they run on dualreg_engine.py.
 ``CoarseWithOffsetModel`` / ``CoarseOffsetLoss`` (reference :591-850, model_type 'hybrid') are constructed directly too and
-run on hybrid_engine.py.  Functional gaps raise NotImplementedError: model_type 'lite' (and 'hybrid' / 'dual_reg' through
-the factory), ``bilinear=False``, and an input size different from ``output_size`` (the bilinear resize of the logits / offset features; train_coarse_depth.py
+run on hybrid_engine.py.  ``CoarseDepthLite`` (reference :199-287, model_type 'lite') is constructed directly as well and
+runs on coarse_engine.CoarseLiteEngine.  Functional gaps raise NotImplementedError: model_type 'lite' / 'hybrid' /
+'dual_reg' through the factory, ``bilinear=False``, and an input size different from ``output_size`` (the bilinear resize of the logits / offset features; train_coarse_depth.py
 always feeds images_size inputs).  ``2 <= n_bins <= 512``; back-propagating through the returned ``depth`` in the autograd
 loop additionally needs ``n_bins <= 256`` (adn_bins_bwd), the fused trainer does not.
 """
@@ -153,6 +154,61 @@ class CoarseDepthUNet(nn.Module):
             return self.forward(x)[1]
         from ..coarse_engine import run_coarse_hard
         return run_coarse_hard(self.engine(), x, self.training)
+
+    def get_num_params(self) -> int:
+        return sum(p.numel() for p in self.parameters() if p.requires_grad)
+
+
+class CoarseDepthLite(nn.Module):
+    """Lightweight encoder-decoder for coarse depth classification (reference :199-287): five Conv2d(k4, s2, p1, bias) ->
+    BatchNorm2d -> LeakyReLU(0.2), five ConvTranspose2d(k4, s2, p1, bias) -> BatchNorm2d -> ReLU without skips, a biased 3x3
+    class head.  ``forward(x) -> (logits [B, n_bins, H, W], depth [B, 1, H, W])`` runs on coarse_engine.CoarseLiteEngine:
+    the k4 geometries of adn_igemm with post-activation BatchNorm (dc_engine.ConvS2BNLeaky / ConvT2BNReLU), and the same
+    fused loss tail as CoarseDepthUNet.  Constructed directly (``init_net(CoarseDepthLite(...), 'kaiming')`` is what the
+    reference's factory does); ``torch.manual_seed(s)`` before the constructor + ``init_weights(net, 'kaiming')`` give the
+    reference's weights.  The inner Sequentials only hold the parameters.  No ``predict_depth`` (the reference has none).
+    Channel widths that are multiples of 64 run on the MFMA kernels; others (the default 48) are correct but take the
+    generic ``direct`` form of adn_igemm."""
+
+    def __init__(self, input_channels: int = 2, n_bins: int = 128, base_channels: int = 48, output_size: int = 256):
+        super().__init__()
+        self.n_bins = n_bins
+        self.output_size = output_size
+        self.input_channels = input_channels
+        b = base_channels
+        enc, c = [], input_channels
+        for w in (b, b * 2, b * 4, b * 8, b * 8):
+            enc += [nn.Conv2d(c, w, 4, 2, 1), nn.BatchNorm2d(w), nn.LeakyReLU(0.2, inplace=True)]
+            c = w
+        self.encoder = nn.Sequential(*enc)
+        dec = []
+        for w in (b * 8, b * 4, b * 2, b, b):
+            dec += [nn.ConvTranspose2d(c, w, 4, 2, 1), nn.BatchNorm2d(w), nn.ReLU(inplace=True)]
+            c = w
+        self.decoder = nn.Sequential(*dec)
+        self.head = nn.Conv2d(b, n_bins, 3, 1, 1)
+        self.register_buffer('bin_centers', torch.linspace(0, 1, n_bins))
+        self._engine = None
+        self.compute_dtype = default_compute_dtype()
+
+    def set_bin_centers(self, bin_centers: torch.Tensor):
+        """Set bin centers for depth reconstruction (in place when the shape allows: a captured step reads the buffer)."""
+        if bin_centers.shape == self.bin_centers.shape:
+            self.bin_centers.copy_(bin_centers.detach())
+        else:
+            self.bin_centers = bin_centers.to(self.bin_centers.device)
+
+    def engine(self):
+        from ..coarse_engine import CoarseLiteEngine
+        if self._engine is None or self._engine.requested_dtype != self.compute_dtype:
+            object.__setattr__(self, '_engine', CoarseLiteEngine(self, self.compute_dtype))
+        return self._engine
+
+    def forward(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """x [B, C, H, W] -> (logits [B, n_bins, H, W] f32, depth [B, 1, H, W] f32).  In training mode under autograd both
+        hang off one autograd node, so the reference's ``criterion(logits, depth, ...)['total'].backward()`` loop works."""
+        from ..coarse_engine import run_coarse
+        return run_coarse(self.engine(), x, self.training)
 
     def get_num_params(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
@@ -511,7 +567,8 @@ def init_net(net, init_type='kaiming', init_gain=0.02, gpu_ids=[]):
 
 
 _UNBUILT = {
-    'lite': "model_type 'lite' (CoarseDepthLite: k4 s2 conv / transposed-conv stack with biases) is not implemented",
+    'lite': "model_type 'lite' is not built by this factory yet: construct CoarseDepthLite directly and call "
+            "init_net(net, 'kaiming'), as train_coarse_depth does",
     'hybrid': "model_type 'hybrid' is not built by this factory (nor by the reference's): construct "
               "CoarseWithOffsetModel directly, as train_coarse_depth does",
     'dual_reg': "model_type 'dual_reg' is not built by this factory (nor by the reference's): construct "

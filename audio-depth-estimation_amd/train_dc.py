@@ -437,8 +437,8 @@ def warm_restart_lr(epoch, base_lr, T_0=20, T_mult=2, eta_min=1e-6):
 
 
 def main_coarse(argv=None):
-    """The reference's train_coarse_depth.py:133-645 for model_type 'unet', 'hybrid' and 'dual_reg'.  'unet':
-    CoarseDepthUNet, CoarseDepthLoss (soft CE, or focal with --use_focal) with valid = depth > 0, targets binned on the
+    """The reference's train_coarse_depth.py:133-645 for model_type 'unet', 'lite', 'hybrid' and 'dual_reg'.  'unet':
+    CoarseDepthUNet ('lite': CoarseDepthLite, constructed directly + init_net(.., 'kaiming')), CoarseDepthLoss (soft CE, or focal with --use_focal) with valid = depth > 0, targets binned on the
     device.  'hybrid': CoarseWithOffsetModel constructed directly (:293-301), CoarseOffsetLoss(--ce_weight,
     --regression_weight, --offset_reg_weight, 'l1', label_smoothing=0.1) over every pixel (:336-343), targets binned on the
     device, validation on the final depth.  'dual_reg': DualRegressionModel constructed directly (:282-288),
@@ -450,8 +450,8 @@ def main_coarse(argv=None):
     from .dataloader.utils_dataset import compute_bins
     from .dualreg_engine import DualRegressionTrainer
     from .hybrid_engine import HybridTrainer
-    from .models.coarse_depth_model import (CoarseDepthLoss, CoarseOffsetLoss, CoarseWithOffsetModel, DualRegressionLoss,
-                                            DualRegressionModel, define_coarse_depth_model)
+    from .models.coarse_depth_model import (CoarseDepthLite, CoarseDepthLoss, CoarseOffsetLoss, CoarseWithOffsetModel,
+                                            DualRegressionLoss, DualRegressionModel, define_coarse_depth_model, init_net)
     p = argparse.ArgumentParser(description='Train Coarse Depth Classification Model (MI355X)')
     p.add_argument('--dataset', type=str, default='batvisionv2', choices=['batvisionv1', 'batvisionv2'])
     p.add_argument('--sparse_method', type=str, default='downup_015')
@@ -498,6 +498,9 @@ def main_coarse(argv=None):
         model = DualRegressionModel(input_channels=2, base_channels=args.base_channels, output_size=S)
     elif hybrid:            # likewise (:293-301)
         model = CoarseWithOffsetModel(input_channels=2, n_bins=args.n_bins, base_channels=args.base_channels, output_size=S)
+    elif args.model_type == 'lite':     # what the reference's factory does for 'lite' (coarse_depth_model.py:518-524, :538)
+        model = init_net(CoarseDepthLite(input_channels=2, n_bins=args.n_bins, base_channels=args.base_channels,
+                                         output_size=S), 'kaiming')
     else:
         model = define_coarse_depth_model(model_type=args.model_type, input_channels=2, n_bins=args.n_bins,
                                           base_channels=args.base_channels, output_size=S)

@@ -523,6 +523,14 @@ int adn_convt_n1_forward_ex(int32_t dtype, int32_t B, int32_t Hs, int32_t Ws, co
  *   channels_last), outputs bf16 [B][Hs][Ws][64]: leaky (slope) and / or relu copy of the conv result.  Ws % 16 == 0. */
 int adn_l0_forward(const float* x, const float* w, int32_t B, int32_t Hs, int32_t Ws, int32_t cin,
                    int32_t cout, float slope, void* out_leaky, void* out_relu, void* stream);
+/* adn_l0_forward_stats: the same first conv in front of a train-mode BatchNorm -- CoarseDepthLite's
+ *   nn.Conv2d(2, 64, 4, 2, 1) + nn.BatchNorm2d (models/coarse_depth_model.py:218-219 of the reference): z = conv(x) +
+ *   bias (bias f32 [64] or NULL) as bf16 [B][Hs][Ws][64], and adn_l0_forward_stats_num_partials rows [2][64] of sum z
+ *   and sum z^2 (one row per workgroup, fixed summation order, taken from the f32 z before the bf16 rounding exactly as
+ *   ADN_EPI_Z_STATS) for adn_bn_fwd_finalize.  cin == 2, cout == 64, Ws % 16 == 0, else ADN_ERR_ARG (num_partials: -1). */
+int64_t adn_l0_forward_stats_num_partials(int32_t B, int32_t Hs, int32_t Ws);
+int adn_l0_forward_stats(const float* x, const float* w, const float* bias, int32_t B, int32_t Hs, int32_t Ws,
+                         int32_t cin, int32_t cout, void* z, float* partials, void* stream);
 /* adn_d0_dgrad: dz f32 [B][2Hs][2Ws] (gradient of the 1-channel output before the final activation), w f32 [128][16]
  *   ([Cin][kh][kw][1]); seg0 / seg1 = skip / up half of the 128 input channels (64 each, bf16 NHWC): out0 = dIn masked
  *   by ref > 0 (else * slope); seg1 may carry BatchNorm-backward statistics (z, mean, istd, partials: one row of
