@@ -14,7 +14,7 @@ from __future__ import annotations
 import torch
 
 from . import kernels as K
-from .dc_engine import Act, ConvBNReLU, DCEngine, Head1x1, Op, flag_solo, mark_tail_writers
+from .dc_engine import Act, ConvBNReLU, DCEngine, Head1x1, Op, tape_records
 from .trainer import OptimTail
 from ._lib import EPI_ACT, EPI_ADD, GEMM_S1
 
@@ -170,7 +170,6 @@ class AdaBinsEngine(DCEngine):
         self.feat_coef = None
         self.feat_stats = None
         self.feat_extra = None       # autograd path: upstream gradients of x1..x5 (see backward_leaves)
-        self.autograd_pass = 0       # forward count of the student branch: a stale backward is refused
         self.branches = {}
 
     def bind_parameters(self):
@@ -202,84 +201,58 @@ class AdaBinsEngine(DCEngine):
         br.class_op = ConvLinear(d1, dec.class_head, br.logits)
         br.head = Head1x1(d1, m.residual_head, 2, 0.05 * m.max_depth)
         br.ops, br.feats, br.d1 = ops, feats, d1
+        br.acts = tape_records(ops + [br.class_op])
         if not needs_grad:
-            for op in ops + [br.class_op]:
-                for a in list(getattr(op, 'srcs', [])) + [getattr(op, 'src', None), getattr(op, 'out', None)]:
-                    if a is not None:
-                        a.needs_grad = False
+            for a in br.acts:
+                a.needs_grad = False
         return br
 
     def _prepare_branches(self, B, H, W, dev):
-        if not self._bound():
-            self.bind_parameters()
-        key = (B, H, W, dev)
-        if self._shape_enter(key):
-            return
+        self._setup((B, H, W), dev)
+
+    def _tape(self, B, H, W):
+        """Two tapes back to back (teacher, student); they share no record."""
         m = self.module
         # output_size != input size: the reference resizes logits and residual with mode='nearest' before the per-pixel
         # softmax expectation / tanh / clamp (:196-198, 334-337, 383-386); per-pixel maps commute with a nearest resize, so
         # the forward outputs are computed at the input resolution and resized at the end (_outputs).  The fused TRAINING
         # step exists for output_size == input size only (what train_adabins_distillation.py uses); it raises otherwise.
         self.resize_to = m.output_size if (H != m.output_size or W != m.output_size) else None
-        self.B, self.dev = B, dev
-        self._scratch = {}
-        self.epc = 8 if self.dtype == torch.bfloat16 else 4
-        self.pairs = []
         self.branches = {
             'rgb': self._build_branch('rgb', 0, 3, m.rgb_encoder, m.rgb_bin_predictor, m.rgb_decoder, B, H, W, False),
             'audio': self._build_branch('audio', 1, 2, m.audio_encoder, m.audio_bin_predictor, m.audio_decoder, B, H, W,
                                         True),
         }
+        return [op for br in self.branches.values() for op in br.ops + [br.class_op, br.head]]
+
+    def _workspace_floor(self, B, H, W):
+        nb = self.module.n_bins
+        return max([1 << 16, K.pool_workspace_bytes(B, H * W, nb, 1), K.bins_bwd_workspace_bytes(B, H * W, nb)] +
+                   [K.pool_workspace_bytes(B, f.H * f.W, f.C, 3) for br in self.branches.values() for f in br.feats])
+
+    def _alloc_outputs(self, B, H, W):
+        m, dev = self.module, self.dev
         f32 = dict(dtype=torch.float32, device=dev)
-        ws = 1 << 16
-        self.ops = []
         for br in self.branches.values():
-            allops = br.ops + [br.class_op]
-            acts = {}
-            for op in allops:
-                for a in list(getattr(op, 'srcs', [])) + [getattr(op, 'src', None), getattr(op, 'out', None)]:
-                    if a is not None:
-                        acts[id(a)] = a
-            br.acts = list(acts.values())
-            for a in br.acts:
-                flag_solo(a)
-                a.alloc(B, self.dtype, dev)
-            mark_tail_writers(allops + [br.head])
-            for op in allops + [br.head]:
-                op.prepare(self)
-                ws = max(ws, op.workspace_bytes(self))
-            self.ops += allops                           # (weight packing walks self.ops)
-            pix = B * H * W
-            br.base = torch.empty(pix, **f32)
+            br.base = torch.empty(B * H * W, **f32)
             br.final = torch.empty(B, 1, H, W, **f32)
             br.mean_logits = torch.empty(B, m.n_bins, **f32)
-            ws = max(ws, K.pool_workspace_bytes(B, H * W, m.n_bins, 1), K.bins_bwd_workspace_bytes(B, H * W, m.n_bins))
-            for f in br.feats:
-                ws = max(ws, K.pool_workspace_bytes(B, f.H * f.W, f.C, 3))
         st = self.branches['audio']
         st.dbase, st.dres = torch.empty(B * H * W, **f32), torch.empty(B * H * W, **f32)
         st.dmean, st.dcent_extra = torch.empty(B, m.n_bins, **f32), torch.empty(B, m.n_bins, **f32)
         self.feat_stats_buf = [torch.empty(B, 3, f.C, **f32) for f in st.feats]
         self.pix_stats = torch.zeros(4, dtype=torch.float64, device=dev)
         self.terms = torch.zeros(8, **f32)
-        self.workspace = torch.empty(ws // 4 + 4, **f32)
-        self.weights_dirty = True
-        self._shape_key = key
 
     # ------------------------------------------------------------------ forward of one branch
     def _forward_branch(self, br, x, training):
-        if not x.is_cuda:
-            raise RuntimeError('AdaBinsDistillationModel needs HIP device tensors (libadn has no CPU path)')
-        x = x.contiguous().float()
+        """``br`` belongs to the current buffer set: the caller made x's shape current (_prepare_branches)."""
         want = 3 if br.name == 'rgb' else 2
         if x.shape[1] != want:
             raise RuntimeError(f'expected input[{list(x.shape)}] to have {want} channels, but got {x.shape[1]} channels instead')
-        self._prepare_branches(x.shape[0], x.shape[2], x.shape[3], x.device)
-        if self.weights_dirty or self._packed_version != self._version_sum():
-            self._pack_weights()
-        K.nchw_slice_to_nhwc(x, 0, want, br.inp.data)
-        for op in br.ops:
-            op.fwd(self, training)
+        self.inputs = [(br.inp, 0, want)]
+        self._begin_forward(x, (x.shape[0], x.shape[2], x.shape[3]))
+        self._forward_ops(br.ops, training)
         if training:                                    # the reference's second decoder pass: same activations, but
             for op in br.dec_bn_ops:                    # every decoder BatchNorm updates its running stats once more
                 op.update_running_stats_again(self)
@@ -321,10 +294,7 @@ class AdaBinsEngine(DCEngine):
     # ------------------------------------------------------------------ backward of the student
     def backward_student(self, dbase, dres, dmean, dcent_extra, logits_extra=None):
         br = self.branches['audio']
-        for a in br.acts:
-            a.written = False
-        self._final = set(id(p) for p, _, _ in self.param_meta if not p.requires_grad)
-        self._wm = len(self.param_meta)
+        self._begin_backward(br.acts)
         br.head.bwd_head(self, dres)
         K.bins_bwd(br.logits.data, br.centers, br.base, dbase, dmean, br.logits.grad, br.dcent, self.workspace)
         if dcent_extra is not None:
@@ -333,14 +303,12 @@ class AdaBinsEngine(DCEngine):
             lg = br.logits
             K.bcast_add(lg.grad.view(-1, 1, 1, lg.C), logits_extra.view(-1, lg.C), 1.0, accumulate=True)
         br.class_op.bwd(self)
-        for op in reversed(br.ops):
-            if op.out.needs_grad:
-                op.bwd(self)
+        self._backward_ops(br.ops)
 
 
 def _f32_add_(dst, src):
-    """dst += src for flat f32 device tensors (adn_bcast_add with one pixel per row)."""
-    K.bcast_add(dst.view(-1, 1, 1, 1), src.contiguous().view(-1, 1), 1.0, accumulate=True)
+    """dst += src for flat f32 device tensors (adn_bcast_add with one pixel per row); ``src`` of any float dtype."""
+    K.bcast_add(dst.view(-1, 1, 1, 1), src.contiguous().float().view(-1, 1), 1.0, accumulate=True)
 
 
 def _backward_leaves(eng, g_feats, g_centers, g_logits, g_base, g_res, g_final):
@@ -360,9 +328,9 @@ def _backward_leaves(eng, g_feats, g_centers, g_logits, g_base, g_res, g_final):
         _f32_add_(dbase, masked)
         _f32_add_(dres, masked)
     if g_base is not None:
-        _f32_add_(dbase, g_base.float())
+        _f32_add_(dbase, g_base)
     if g_res is not None:
-        _f32_add_(dres, g_res.float())
+        _f32_add_(dres, g_res)
     eng.feat_extra = None
     if any(g is not None for g in g_feats):
         eng.feat_extra = []
@@ -414,8 +382,8 @@ class _StudentFunction(torch.autograd.Function):
     def backward(ctx, *g):
         eng = ctx.engine
         if ctx.stamp != eng.autograd_pass:
-            raise RuntimeError('AdaBinsDistillationModel: backward through a forward whose activations were overwritten '
-                               'by a later training forward of the same module')
+            raise RuntimeError('AdaBinsDistillationModel: backward through a forward whose activations were '
+                               'overwritten by a later training forward of the same module')
         g_logits, g_base, g_res, g_final = g[7], g[8], g[9], g[10]
         if eng.resize_to is not None:          # the returned maps are nearest-resized: gradients back through the gather
             H, W = eng.branches['audio'].logits.H, eng.branches['audio'].logits.W

@@ -11,7 +11,8 @@ from __future__ import annotations
 import torch
 
 from . import kernels as K
-from .dc_engine import DCEngine, Head1x1, flag_solo, mark_tail_writers
+from .adabins_engine import _f32_add_
+from .dc_engine import DCEngine, Head1x1, decoder_ops, run_engine, unet_encoder_ops
 from .trainer import OptimTail
 
 
@@ -19,73 +20,42 @@ class BaseResidualEngine(DCEngine):
     def __init__(self, module, compute_dtype=torch.bfloat16):
         super().__init__(module, None, compute_dtype, 'BaseResidualDepthNet')
 
-    def _prepare_net(self, x):
-        if not self._bound():
-            self.bind_parameters()
-        B, Cin, H, W = x.shape
-        key = (B, Cin, H, W, x.device)
-        if self._shape_enter(key):
-            return
+    def check_input(self, shape):
+        B, Cin, H, W = shape
+        if Cin != self.module.input_channels:
+            raise RuntimeError(f'expected input[{B}, {Cin}, {H}, {W}] to have {self.module.input_channels} channels, but got '
+                               f'{Cin} channels instead')
+
+    def _out_size(self, H, W):
+        """input size != output_size: both heads resize their ACTIVATED map (bilinear, align_corners=False) before the sum
+        and the clamp (base_residual_model.py:185-211)"""
+        S = self.module.output_size
+        return S if (H != S or W != S) else None
+
+    def _tape(self, B, Cin, H, W):
         m = self.module
-        if Cin != m.input_channels:
-            raise RuntimeError(f'expected input[{B}, {Cin}, {H}, {W}] to have {m.input_channels} channels, but got {Cin} '
-                               'channels instead')
-        # input size != output_size: both heads resize their ACTIVATED map (bilinear, align_corners=False) before the sum
-        # and the clamp (base_residual_model.py:185-211)
-        S = m.output_size
-        osz = S if (H != S or W != S) else None
-        self.B, self.dev = B, x.device
-        self._scratch = {}
-        self.epc = 8 if self.dtype == torch.bfloat16 else 4
-        self.pairs = []
+        osz = self._out_size(H, W)
         inp = self.thin_input('x', Cin, H, W)
-        ops, f = m.inc.adn_ops([inp], 'x1', H, W)
-        feats = [f]
-        for i, down in enumerate((m.down1, m.down2, m.down3, m.down4)):
-            o, f = down.adn_ops(feats[-1], f'x{i + 2}')
-            ops += o
-            feats.append(f)
-        ends = {}
-        for tag, ups in (('base', (m.base_up1, m.base_up2, m.base_up3, m.base_up4)),
-                         ('res', (m.res_up1, m.res_up2, m.res_up3, m.res_up4))):
-            d = feats[4]
-            for i, up in enumerate(ups):
-                o, d = up.adn_ops(d, feats[3 - i], f'{tag}.d{4 - i}')
-                ops += o
-            ends[tag] = d
-        self.inputs, self.ops = [(inp, 0, Cin)], ops
-        self.head_base = Head1x1(ends['base'], m.base_head, 1, m.max_depth, osz, clamp_after_resize=False)   # sigmoid * max_depth
-        self.head_res = Head1x1(ends['res'], m.res_head, 2, 0.3 * m.max_depth, osz, clamp_after_resize=False)  # tanh * 0.3 max_depth
-        acts = {}
-        for op in ops:
-            for a in list(getattr(op, 'srcs', [])) + [getattr(op, 'src', None), getattr(op, 'out', None)]:
-                if a is not None:
-                    acts[id(a)] = a
-        self.acts = list(acts.values())
-        for a in self.acts:
-            flag_solo(a)
-            a.alloc(B, self.dtype, x.device)
-        mark_tail_writers(ops + [self.head_base, self.head_res])
-        ws = 1 << 16
-        for op in ops + [self.head_base, self.head_res]:
-            op.prepare(self)
-            ws = max(ws, op.workspace_bytes(self))
-        f32 = dict(dtype=torch.float32, device=x.device)
-        self.final = torch.empty(B, 1, S, S, **f32) if osz else torch.empty(B, 1, H, W, **f32)
-        self.workspace = torch.empty(max(ws, K.lowpass_workspace_bytes(B, H, W, 64)) // 4 + 4, **f32)
-        self.weights_dirty = True
-        self._shape_key = key
+        self.inputs = [(inp, 0, Cin)]
+        ops, feats = unet_encoder_ops(m, inp, H, W)
+        o, d = decoder_ops((m.base_up1, m.base_up2, m.base_up3, m.base_up4), feats, 'base')
+        ops += o
+        self.head_base = Head1x1(d, m.base_head, 1, m.max_depth, osz, clamp_after_resize=False)   # sigmoid * max_depth
+        o, d = decoder_ops((m.res_up1, m.res_up2, m.res_up3, m.res_up4), feats, 'res')
+        ops += o
+        self.head_res = Head1x1(d, m.res_head, 2, 0.3 * m.max_depth, osz, clamp_after_resize=False)  # tanh * 0.3 max_depth
+        return ops + [self.head_base, self.head_res]
+
+    def _workspace_floor(self, B, Cin, H, W):
+        return max(1 << 16, K.lowpass_workspace_bytes(B, H, W, 64))
+
+    def _alloc_outputs(self, B, Cin, H, W):
+        S = self._out_size(H, W)
+        self.final = torch.empty(B, 1, S or H, S or W, dtype=torch.float32, device=self.dev)
 
     def forward_net(self, x, training):
-        if not x.is_cuda:
-            raise RuntimeError('BaseResidualDepthNet needs a HIP device tensor (libadn has no CPU path)')
-        x = x.contiguous().float()
-        self._prepare_net(x)
-        if self.weights_dirty or self._packed_version != self._version_sum():
-            self._pack_weights()
-        self.load_input(x)
-        for op in self.ops:
-            op.fwd(self, training)
+        self._begin_forward(x)
+        self._forward_ops(self.ops, training)
         self.head_base.fwd(self, training)
         self.head_res.fwd(self, training)
         K.clamp_add(self.head_base.result, self.head_res.result, self.module.max_depth, self.final)
@@ -95,62 +65,34 @@ class BaseResidualEngine(DCEngine):
         b, r, f = self.forward_net(x, training)
         return b.clone(), r.clone(), f.clone()
 
-    def backward_net(self, dbase, dres):
-        for a in self.acts:
-            a.written = False
-        self._final = set(id(p) for p, _, _ in self.param_meta if not p.requires_grad)
-        self._wm = len(self.param_meta)
-        self.head_res.bwd_head(self, dres)
-        self.head_base.bwd_head(self, dbase)
-        for op in reversed(self.ops):
-            if op.out.needs_grad:
-                op.bwd(self)
-
-
-class _BaseResidualFunction(torch.autograd.Function):
-    """torch.autograd bridge: parameters are inputs, the outputs are (base_depth, residual, final_depth), so
-    ``criterion(base, res, final, gt, mask)[0].backward()`` of train_base_residual.py reaches the parameters.
-    final = clamp(base + residual, 0, max_depth) (base_residual_model.py:150-152) routes its gradient into both heads."""
-
-    @staticmethod
-    def forward(ctx, x, engine, *params):
-        b, r, f = engine.forward_net(x, True)
-        engine.autograd_pass = getattr(engine, 'autograd_pass', 0) + 1
-        ctx.engine, ctx.stamp = engine, engine.autograd_pass
-        ctx.set_materialize_grads(False)
-        return b.clone(), r.clone(), f.clone()
-
-    @staticmethod
-    def backward(ctx, g_base, g_res, g_final):
-        eng = ctx.engine
-        if ctx.stamp != eng.autograd_pass:
-            raise RuntimeError('BaseResidualDepthNet: backward through a forward whose activations were overwritten by a '
-                               'later training forward of the same module')
-        base, resid = eng.head_base.result, eng.head_res.result
-        add_ = lambda dst, src: K.bcast_add(dst.view(-1, 1, 1, 1), src.contiguous().float().view(-1, 1), 1.0, accumulate=True)
+    def route_grads(self, g_base, g_res, g_final):
+        """(dbase, dres) of the autograd bridge: final = clamp(base + residual, 0, max_depth)
+        (base_residual_model.py:150-152) routes its gradient into both heads."""
+        base, resid = self.head_base.result, self.head_res.result
         dbase, dres = torch.zeros_like(base), torch.zeros_like(resid)
         if g_final is not None:
             s = base.clone()
-            add_(s, resid)
+            _f32_add_(s, resid)
             masked = torch.empty_like(s)
-            K.clamp_range(s, eng.module.max_depth, masked, g=g_final.contiguous().float())
-            add_(dbase, masked)
-            add_(dres, masked)
+            K.clamp_range(s, self.module.max_depth, masked, g=g_final.contiguous().float())
+            _f32_add_(dbase, masked)
+            _f32_add_(dres, masked)
         if g_base is not None:
-            add_(dbase, g_base)
+            _f32_add_(dbase, g_base)
         if g_res is not None:
-            add_(dres, g_res)
-        eng.backward_net(dbase, dres)
-        return (None, None) + tuple(eng.grad_view(p) if p.requires_grad else None for p, _, _ in eng.param_meta)
+            _f32_add_(dres, g_res)
+        return dbase, dres
+
+    def backward_net(self, dbase, dres):
+        self._begin_backward(self.acts)
+        self.head_res.bwd_head(self, dres)
+        self.head_base.bwd_head(self, dbase)
+        self._backward_ops(self.ops)
 
 
-def run_base_residual(engine, x, training):
-    if not engine._bound():
-        engine.bind_parameters()
-    if training and torch.is_grad_enabled() and any(p.requires_grad for p, _, _ in engine.param_meta):
-        return _BaseResidualFunction.apply(x, engine, *[p for p, _, _ in engine.param_meta])
-    with torch.no_grad():
-        return engine.run(x, training)
+# model(x) in training mode under autograd returns (base_depth, residual, final_depth) hanging off one node, so that
+# ``criterion(base, res, final, gt, mask)[0].backward()`` of train_base_residual.py reaches the parameters
+run_base_residual = run_engine
 
 
 class BaseResidualTrainer(OptimTail):

@@ -901,10 +901,47 @@ def _tail_setup(op, eng, work):
             op.tail = True
 
 
+def tape_records(ops):
+    """The activation records the ops of a tape read or write, each once, in forward order."""
+    acts = {}
+    for op in ops:
+        for a in (list(getattr(op, 'srcs', [])) +
+                  [getattr(op, k, None) for k in ('src', 'out', 'xl', 'xr', 'ol', 'or_')]):
+            if a is not None:
+                acts[id(a)] = a
+    return list(acts.values())
+
+
+def unet_encoder_ops(m, inp, H, W):
+    """``inc`` and ``down1..4`` of a DoubleConv U-Net mirror over the input record -> (ops, [x1..x5])."""
+    ops, f = m.inc.adn_ops([inp], 'x1', H, W)
+    feats = [f]
+    for i, down in enumerate((m.down1, m.down2, m.down3, m.down4)):
+        o, f = down.adn_ops(feats[-1], f'x{i + 2}')
+        ops += o
+        feats.append(f)
+    return ops, feats
+
+
+def decoder_ops(ups, feats, tag):
+    """The four ``Up`` blocks of one decoder over the encoder records x1..x5 -> (ops, last record); the records are
+    named ``<tag>.d4 .. <tag>.d1`` (``d4 .. d1`` without a tag)."""
+    ops, d = [], feats[4]
+    for i, up in enumerate(ups):
+        o, d = up.adn_ops(d, feats[3 - i], f'{tag}.d{4 - i}' if tag else f'd{4 - i}')
+        ops += o
+    return ops, d
+
+
 class DCEngine(FlatParamEngine):
     """Runs a DoubleConv-family module through libadn.  ``build(engine, B, C, H, W)`` (supplied by the model
     mirror) returns (inputs, ops, head): ``inputs`` = [(Act, first channel, channels)] slices of the NCHW network
-    input, the forward op list in execution order, and the output head."""
+    input, the forward op list in execution order, and the output head.
+
+    The tape life cycle is the same for every family and lives here: ``_setup`` (per-shape build), ``_begin_forward``,
+    ``_begin_backward`` / ``_backward_ops``.  A family subclass supplies hooks: ``_tape`` (its ops), ``check_input``,
+    ``_workspace_floor``, ``_alloc_outputs``, and for the autograd bridge (EngineFunction) ``run`` / ``route_grads`` /
+    ``backward_net``.  ``fwd_serial`` and ``autograd_pass`` count passes of the ENGINE, whatever the input shape."""
 
     def __init__(self, module, build, compute_dtype=torch.bfloat16, model_name='model'):
         self.module = module
@@ -915,7 +952,8 @@ class DCEngine(FlatParamEngine):
         self.requested_dtype = compute_dtype
         self.mx8 = compute_dtype == torch.float8_e4m3fn
         self.dtype = torch.bfloat16 if self.mx8 else compute_dtype
-        self.fwd_serial = 0
+        self.fwd_serial = 0          # forward passes so far: the fp8 operand copy of a record belongs to one of them
+        self.autograd_pass = 0       # training forwards through the autograd bridge so far: a stale backward is refused
         self.model_name = model_name
         self.depth_norm = False
         self._init_flat()
@@ -937,37 +975,52 @@ class DCEngine(FlatParamEngine):
             act.q8_serial = self.fwd_serial
         return act.q8, act.q8s
 
-    def _prepare(self, x):
+    # ------------------------------------------------------------------ hooks of a family
+    def check_input(self, shape):
+        """Host-only: raise for an input shape the family does not run."""
+
+    def _tape(self, B, Cin, H, W):
+        """Build the ops of one input shape, set ``inputs`` (and whatever the family's forward / backward walk), and
+        return the tape: every op in forward order with the heads in place."""
+        self.inputs, ops, self.head = self._build(self, B, Cin, H, W)
+        return ops + [self.head]
+
+    def _workspace_floor(self, *shape):
+        """Bytes of the shared workspace that the family's own kernels (loss, targets ...) need."""
+        return 16
+
+    def _alloc_outputs(self, *shape):
+        """Per-shape output buffers of the family (final, depth, coarse, centers ...)."""
+
+    # ------------------------------------------------------------------ life cycle
+    def _setup(self, shape, dev):
+        """Make ``shape`` (what the hooks take: B, Cin, H, W) on ``dev`` the current buffer set, building it on first use."""
         if not self._bound():
             self.bind_parameters()
-        B, Cin, H, W = x.shape
-        key = (B, Cin, H, W, x.device)
+        key = tuple(shape) + (dev,)
         if self._shape_enter(key):
             return
-        self.B, self.dev = B, x.device
+        self.check_input(shape)
+        B = shape[0]
+        self.B, self.dev = B, dev
         self._scratch = {}
-        epc = 8 if self.dtype == torch.bfloat16 else 4
-        self.epc = epc
+        self.epc = 8 if self.dtype == torch.bfloat16 else 4
         self.pairs = []
-        self.inputs, self.ops, self.head = self._build(self, B, Cin, H, W)
-        acts = {}
-        for op in self.ops:
-            for a in (list(getattr(op, 'srcs', [])) +
-                      [getattr(op, k, None) for k in ('src', 'out', 'xl', 'xr', 'ol', 'or_')]):
-                if a is not None:
-                    acts[id(a)] = a
-        self.acts = list(acts.values())
+        tape = self._tape(*shape)
+        self.ops = [op for op in tape if not isinstance(op, Head1x1)]      # (weight packing walks self.ops)
+        self.acts = tape_records(self.ops)
         for a, b in self.pairs:                       # inputs of an aliasing pair are stacked before its outputs
-            stack_pair(a, b, B, self.dtype, x.device)
+            stack_pair(a, b, B, self.dtype, dev)
         for a in self.acts:
             flag_solo(a)
-            a.alloc(B, self.dtype, x.device)
-        mark_tail_writers(self.ops + [self.head])
-        ws = 16
-        for op in self.ops + [self.head]:
+            a.alloc(B, self.dtype, dev)
+        mark_tail_writers(tape)
+        ws = self._workspace_floor(*shape)
+        for op in tape:
             op.prepare(self)
             ws = max(ws, op.workspace_bytes(self))
-        self.workspace = torch.empty(ws // 4 + 4, dtype=torch.float32, device=x.device)
+        self._alloc_outputs(*shape)
+        self.workspace = torch.empty(ws // 4 + 4, dtype=torch.float32, device=dev)
         self.weights_dirty = True
         self._shape_key = key
 
@@ -996,17 +1049,26 @@ class DCEngine(FlatParamEngine):
         for act, c_lo, c in self.inputs:
             K.nchw_slice_to_nhwc(x, c_lo, c, act.data)
 
-    def forward(self, x, training):
+    def _begin_forward(self, x, shape=None):
+        """What every forward starts with: refuse a host tensor, make the shape current, repack stale weight operands,
+        advance ``fwd_serial`` and load the network input.  -> the contiguous f32 input."""
         if not x.is_cuda:
-            raise RuntimeError(f'{self.model_name}.forward needs a HIP device tensor (libadn has no CPU path)')
+            raise RuntimeError(f'{self.model_name} needs a HIP device tensor (libadn has no CPU path)')
         x = x.contiguous().float()
-        self._prepare(x)
+        self._setup(tuple(x.shape) if shape is None else shape, x.device)
         if self.weights_dirty or self._packed_version != self._version_sum():
             self._pack_weights()
         self.fwd_serial += 1
         self.load_input(x)
-        for op in self.ops:
+        return x
+
+    def _forward_ops(self, ops, training):
+        for op in ops:
             op.fwd(self, training)
+
+    def forward(self, x, training):
+        self._begin_forward(x)
+        self._forward_ops(self.ops, training)
         self.head.fwd(self, training)
         return self.head.result
 
@@ -1028,18 +1090,26 @@ class DCEngine(FlatParamEngine):
                 off = self.param_meta[idx][1]
                 _lib.record_py(lambda: self.on_grad_ready(off))
 
-    def backward(self, gout, fused_norm=False, dz_ready=False):
-        """gout: d loss / d output, f32 [B,1,H,W].  Fills flat_g (all parameters).  ``fused_norm`` / ``dz_ready`` are
-        the U-Net engine's options (this one offers neither: supports_fused_norm, dz_target) and are ignored."""
-        for a in self.acts:
+    def _begin_backward(self, acts):
+        """What every backward starts with: no record of ``acts`` has a gradient yet, no trainable parameter's gradient
+        is final, the watermark sits at the end of the flat gradient buffer."""
+        for a in acts:
             a.written = False
         self._final = set(id(p) for p, _, _ in self.param_meta if not p.requires_grad)
         self._wm = len(self.param_meta)
-        gout = gout.contiguous().float()
-        self.head.bwd_head(self, gout)
-        for op in reversed(self.ops):
+
+    def _backward_ops(self, ops):
+        for op in reversed(ops):
             if op.out.needs_grad:
                 op.bwd(self)
+
+    def backward(self, gout, fused_norm=False, dz_ready=False):
+        """gout: d loss / d output, f32 [B,1,H,W].  Fills flat_g (all parameters).  ``fused_norm`` / ``dz_ready`` are
+        the U-Net engine's options (this one offers neither: supports_fused_norm, dz_target) and are ignored."""
+        self._begin_backward(self.acts)
+        gout = gout.contiguous().float()
+        self.head.bwd_head(self, gout)
+        self._backward_ops(self.ops)
         if self.on_grad_ready is not None:
             _lib.record_py(lambda: self.on_grad_ready(0))
 
@@ -1078,3 +1148,38 @@ def run_dcnet(engine, x, training):
         return _DCFunction.apply(x, engine, training, *[p for p, _, _ in engine.param_meta])
     with torch.no_grad():
         return engine.forward(x, training).clone()
+
+
+class EngineFunction(torch.autograd.Function):
+    """torch.autograd bridge of a multi-output family: the parameters are inputs, the outputs are what the engine's
+    ``run(x, True)`` returns, so the reference's ``criterion(*model(x), ...).backward(); clip; optimizer.step()`` loops run
+    unchanged.  ``engine.route_grads(*upstream)`` (any of them may be None: counts as zero) forms the arguments of
+    ``engine.backward_net``.  A backward through a forward that a later training forward overwrote is refused."""
+
+    @staticmethod
+    def forward(ctx, x, engine, *params):
+        out = engine.run(x, True)
+        engine.autograd_pass += 1
+        ctx.engine, ctx.stamp = engine, engine.autograd_pass
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, *grads):
+        eng = ctx.engine
+        if ctx.stamp != eng.autograd_pass:
+            raise RuntimeError(f'{eng.model_name}: backward through a forward whose activations were '
+                               'overwritten by a later training forward of the same module')
+        eng.backward_net(*eng.route_grads(*grads))
+        return (None, None) + tuple(eng.grad_view(p) if p.requires_grad else None for p, _, _ in eng.param_meta)
+
+
+def run_engine(engine, x, training):
+    """``model(x)`` of a family with ``run`` / ``route_grads`` / ``backward_net``: differentiable outputs in training mode
+    under grad, plain values otherwise."""
+    if not engine._bound():
+        engine.bind_parameters()
+    if training and torch.is_grad_enabled() and any(p.requires_grad for p, _, _ in engine.param_meta):
+        return EngineFunction.apply(x, engine, *[p for p, _, _ in engine.param_meta])
+    with torch.no_grad():
+        return engine.run(x, training)

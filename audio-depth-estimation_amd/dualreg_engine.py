@@ -20,7 +20,8 @@ from __future__ import annotations
 import torch
 
 from . import kernels as K
-from .dc_engine import Act, ConvBNReLU, DCEngine, Head1x1, flag_solo, mark_tail_writers
+from .adabins_engine import _f32_add_
+from .dc_engine import Act, ConvBNReLU, DCEngine, Head1x1, decoder_ops, run_engine, unet_encoder_ops
 from .trainer import OptimTail
 
 
@@ -29,10 +30,7 @@ def offset_branch_ops(eng, feats, ups, fusion, head_conv, tag='offset'):
     ``feats`` (x1..x5), the plane record of ``eng.plane_channels`` channels that the caller fills with the detached
     coarse depth before these ops run, ``fusion`` = Sequential(conv3x3 + bias, BN, ReLU, conv3x3 + bias, BN, ReLU) and the
     1x1 ``head_conv`` with identity activation.  -> (ops in forward order, plane record, Head1x1)."""
-    ops, d = [], feats[4]
-    for i, up in enumerate(ups):
-        o, d = up.adn_ops(d, feats[3 - i], f'{tag}.d{4 - i}')
-        ops += o
+    ops, d = decoder_ops(ups, feats, tag)
     plane = Act(f'{tag}.coarse_plane', eng.plane_channels, d.H, d.W, needs_grad=False)
     plane.C_real = 1
     mid = Act(f'{tag}.fuse0', fusion[0].out_channels, d.H, d.W)
@@ -42,13 +40,14 @@ def offset_branch_ops(eng, feats, ups, fusion, head_conv, tag='offset'):
     return ops, plane, Head1x1(fused, head_conv, 3, 0.0)
 
 
-class DualRegEngine(DCEngine):
-    def __init__(self, module, compute_dtype=torch.bfloat16, plane_channels=None):
-        super().__init__(module, None, compute_dtype, 'DualRegressionModel')
+class OffsetBranch:
+    """Engine mixin of the two families with an offset branch: the width of the plane record (``requested_plane``: None,
+    'epc' or a channel count), the square-input refusal, and the branch's forward / backward walks."""
+
+    def _init_plane(self, plane_channels):
         if self.mx8:
-            raise NotImplementedError('DualRegressionModel: the mxfp8 path is not wired for this family')
+            raise NotImplementedError(f'{self.model_name}: the mxfp8 path is not wired for this family')
         self.requested_plane = plane_channels
-        self.autograd_pass = 0
 
     def _plane_width(self):
         epc = 8 if self.dtype == torch.bfloat16 else 4
@@ -58,91 +57,74 @@ class DualRegEngine(DCEngine):
         elif p == 'epc':
             p = epc
         if p < 1 or p % epc != 0:
-            raise ValueError(f'DualRegEngine: plane_channels must be a positive multiple of {epc} (one 16-byte chunk), got {p}')
+            raise ValueError(f'{type(self).__name__}: plane_channels must be a positive multiple of {epc} (one 16-byte chunk), '
+                             f'got {p}')
         return p
 
-    def check_input(self, shape):
-        """Host-only: the input shapes this family runs."""
+    def check_square(self, shape, what):
+        """Host-only: the channel count, and H == W == output_size (``what`` names the resize that is not implemented)."""
         B, Cin, H, W = shape
         m = self.module
         if Cin != m.input_channels:
             raise RuntimeError(f'expected input[{B}, {Cin}, {H}, {W}] to have {m.input_channels} channels, but got {Cin} '
                                'channels instead')
         if H != m.output_size or W != m.output_size:
-            raise NotImplementedError(f'DualRegressionModel: input {H} x {W} != output_size {m.output_size}: the bilinear '
-                                      f'resize of the {m.base_channels}-channel offset features '
-                                      '(coarse_depth_model.py:972-974) is not implemented')
+            raise NotImplementedError(f'{self.model_name}: input {H} x {W} != output_size {m.output_size}: the bilinear '
+                                      f'resize of {what} is not implemented')
 
-    def _prepare_net(self, x):
-        self.check_input(x.shape)
-        if not self._bound():
-            self.bind_parameters()
-        B, Cin, H, W = x.shape
-        key = (B, Cin, H, W, x.device)
-        if self._shape_enter(key):
-            return
+    def offset_branch(self, feats):
+        """-> the offset branch's tape (head last); sets ``plane_channels``, ``ops_offset``, ``plane``, ``head_offset``."""
         m = self.module
-        self.B, self.dev = B, x.device
-        self._scratch = {}
-        self.epc = 8 if self.dtype == torch.bfloat16 else 4
         self.plane_channels = self._plane_width()
-        self.pairs = []
-        inp = self.thin_input('x', Cin, H, W)
-        ops, f = m.inc.adn_ops([inp], 'x1', H, W)
-        feats = [f]
-        for i, down in enumerate((m.down1, m.down2, m.down3, m.down4)):
-            o, f = down.adn_ops(feats[-1], f'x{i + 2}')
-            ops += o
-            feats.append(f)
-        d = feats[4]
-        for i, up in enumerate((m.coarse_up1, m.coarse_up2, m.coarse_up3, m.coarse_up4)):
-            o, d = up.adn_ops(d, feats[3 - i], f'coarse.d{4 - i}')
-            ops += o
-        self.head_coarse = Head1x1(d, m.coarse_head, 3, 0.0)
-        self.ops_coarse = ops                                                 # encoder + coarse decoder
         self.ops_offset, self.plane, self.head_offset = offset_branch_ops(
             self, feats, (m.offset_up1, m.offset_up2, m.offset_up3, m.offset_up4), m.offset_fusion, m.offset_head)
-        self.inputs, self.ops = [(inp, 0, Cin)], self.ops_coarse + self.ops_offset
-        tape = self.ops_coarse + [self.head_coarse] + self.ops_offset + [self.head_offset]
-        acts = {}
-        for op in self.ops:
-            for a in list(getattr(op, 'srcs', [])) + [getattr(op, 'src', None), getattr(op, 'out', None)]:
-                if a is not None:
-                    acts[id(a)] = a
-        self.acts = list(acts.values())
-        for a in self.acts:
-            flag_solo(a)
-            a.alloc(B, self.dtype, x.device)
-        mark_tail_writers(tape)
+        return self.ops_offset + [self.head_offset]
+
+    def forward_offset(self, coarse, training):
+        """The offset branch over the detached ``coarse`` depth (f32 [B,1,H,W]) -> offset, the head's own buffer."""
+        K.nchw_to_nhwc(coarse, self.plane.data)                               # channel 0 = coarse depth, the rest zero
+        self._forward_ops(self.ops_offset, training)
+        self.head_offset.fwd(self, training)
+        return self.head_offset.result
+
+    def backward_offset(self, doffset):
+        self.head_offset.bwd_head(self, doffset)
+        self._backward_ops(self.ops_offset)
+
+
+class DualRegEngine(OffsetBranch, DCEngine):
+    def __init__(self, module, compute_dtype=torch.bfloat16, plane_channels=None):
+        super().__init__(module, None, compute_dtype, 'DualRegressionModel')
+        self._init_plane(plane_channels)
+
+    def check_input(self, shape):
+        self.check_square(shape, f'the {self.module.base_channels}-channel offset features (coarse_depth_model.py:972-974)')
+
+    def _tape(self, B, Cin, H, W):
+        m = self.module
+        inp = self.thin_input('x', Cin, H, W)
+        self.inputs = [(inp, 0, Cin)]
+        ops, feats = unet_encoder_ops(m, inp, H, W)
+        o, d = decoder_ops((m.coarse_up1, m.coarse_up2, m.coarse_up3, m.coarse_up4), feats, 'coarse')
+        self.ops_coarse = ops + o                                             # encoder + coarse decoder
+        self.head_coarse = Head1x1(d, m.coarse_head, 3, 0.0)
+        return self.ops_coarse + [self.head_coarse] + self.offset_branch(feats)
+
+    def _workspace_floor(self, B, Cin, H, W):
         pix = B * H * W
-        ws = max(1 << 16, K.dualreg_loss_workspace_bytes(pix), K.coarse_targets_workspace_bytes(pix))
-        for op in tape:
-            op.prepare(self)
-            ws = max(ws, op.workspace_bytes(self))
-        self.final = torch.empty(B, 1, H, W, dtype=torch.float32, device=x.device)
-        self.workspace = torch.empty(ws // 4 + 4, dtype=torch.float32, device=x.device)
-        self.weights_dirty = True
-        self._shape_key = key
+        return max(1 << 16, K.dualreg_loss_workspace_bytes(pix), K.coarse_targets_workspace_bytes(pix))
+
+    def _alloc_outputs(self, B, Cin, H, W):
+        self.final = torch.empty(B, 1, H, W, dtype=torch.float32, device=self.dev)
 
     def forward_net(self, x, training, head=True):
         """-> (coarse, offset, final), f32 [B,1,H,W], the engine's own buffers.  ``head=False`` (the fused trainer): final
         is left to the caller's own adn_dualreg_loss pass, which writes it together with the loss and the gradients."""
-        if not x.is_cuda:
-            raise RuntimeError('DualRegressionModel needs a HIP device tensor (libadn has no CPU path)')
-        x = x.contiguous().float()
-        self._prepare_net(x)
-        if self.weights_dirty or self._packed_version != self._version_sum():
-            self._pack_weights()
-        self.fwd_serial += 1
-        self.load_input(x)
-        for op in self.ops_coarse:
-            op.fwd(self, training)
+        self._begin_forward(x)
+        self._forward_ops(self.ops_coarse, training)
         self.head_coarse.fwd(self, training)
-        K.nchw_to_nhwc(self.head_coarse.result, self.plane.data)              # channel 0 = coarse depth, the rest zero
-        for op in self.ops_offset:
-            op.fwd(self, training)
-        self.head_offset.fwd(self, training)
-        coarse, offset = self.head_coarse.result, self.head_offset.result
+        coarse = self.head_coarse.result
+        offset = self.forward_offset(coarse, training)
         if head:
             K.dualreg_loss(coarse.view(-1), offset.view(-1), self.final.view(-1))
         return coarse, offset, self.final
@@ -151,58 +133,26 @@ class DualRegEngine(DCEngine):
         c, o, f = self.forward_net(x, training)
         return c.clone(), o.clone(), f.clone()
 
-    def backward_net(self, dcoarse, doffset):
-        """The tape in reverse: offset head, fusion convs and offset decoder, coarse head, coarse decoder, encoder."""
-        for a in self.acts:
-            a.written = False
-        self._final = set(id(p) for p, _, _ in self.param_meta if not p.requires_grad)
-        self._wm = len(self.param_meta)
-        self.head_offset.bwd_head(self, doffset)
-        for op in reversed(self.ops_offset):
-            if op.out.needs_grad:
-                op.bwd(self)
-        self.head_coarse.bwd_head(self, dcoarse)
-        for op in reversed(self.ops_coarse):
-            if op.out.needs_grad:
-                op.bwd(self)
-
-
-class _DualRegFunction(torch.autograd.Function):
-    """torch.autograd bridge: parameters are inputs, the outputs are (coarse, offset, final), so the reference's loop
-    ``criterion(*model(x), gt)[0].backward(); clip_grad_norm_; optimizer.step()`` (train_coarse_depth.py:422-463) runs
-    unchanged.  final = coarse + offset routes its gradient into both heads; missing gradients count as zero."""
-
-    @staticmethod
-    def forward(ctx, x, engine, *params):
-        c, o, f = engine.forward_net(x, True)
-        engine.autograd_pass += 1
-        ctx.engine, ctx.stamp = engine, engine.autograd_pass
-        ctx.set_materialize_grads(False)
-        return c.clone(), o.clone(), f.clone()
-
-    @staticmethod
-    def backward(ctx, g_coarse, g_offset, g_final):
-        eng = ctx.engine
-        if ctx.stamp != eng.autograd_pass:
-            raise RuntimeError('DualRegressionModel: backward through a forward whose activations were overwritten by a '
-                               'later training forward of the same module')
-        add_ = lambda dst, src: K.bcast_add(dst.view(-1, 1, 1, 1), src.contiguous().float().view(-1, 1), 1.0, accumulate=True)
-        dcoarse, doffset = torch.zeros_like(eng.final), torch.zeros_like(eng.final)
+    def route_grads(self, g_coarse, g_offset, g_final):
+        """(dcoarse, doffset) of the autograd bridge: final = coarse + offset routes its gradient into both heads."""
+        dcoarse, doffset = torch.zeros_like(self.final), torch.zeros_like(self.final)
         for g, dsts in ((g_coarse, (dcoarse,)), (g_offset, (doffset,)), (g_final, (dcoarse, doffset))):
             if g is not None:
                 for dst in dsts:
-                    add_(dst, g)
-        eng.backward_net(dcoarse, doffset)
-        return (None, None) + tuple(eng.grad_view(p) if p.requires_grad else None for p, _, _ in eng.param_meta)
+                    _f32_add_(dst, g)
+        return dcoarse, doffset
+
+    def backward_net(self, dcoarse, doffset):
+        """The tape in reverse: offset head, fusion convs and offset decoder, coarse head, coarse decoder, encoder."""
+        self._begin_backward(self.acts)
+        self.backward_offset(doffset)
+        self.head_coarse.bwd_head(self, dcoarse)
+        self._backward_ops(self.ops_coarse)
 
 
-def run_dualreg(engine, x, training):
-    if not engine._bound():
-        engine.bind_parameters()
-    if training and torch.is_grad_enabled() and any(p.requires_grad for p, _, _ in engine.param_meta):
-        return _DualRegFunction.apply(x, engine, *[p for p, _, _ in engine.param_meta])
-    with torch.no_grad():
-        return engine.run(x, training)
+# model(x) in training mode under autograd returns (coarse, offset, final) hanging off one node, so the reference's loop
+# ``criterion(*model(x), gt)[0].backward(); clip_grad_norm_; optimizer.step()`` (train_coarse_depth.py:422-463) runs unchanged
+run_dualreg = run_engine
 
 
 class DualRegressionTrainer(OptimTail):
@@ -250,13 +200,7 @@ class DualRegressionTrainer(OptimTail):
         K.dualreg_loss(coarse.view(-1), offset.view(-1), final.view(-1), gt=gt, n_valid=stats, pixels_global=pix_global,
                        coarse_weight=w[0], final_weight=w[1], offset_reg_weight=w[2], dcoarse=dcoarse.view(-1),
                        doffset=doffset.view(-1), workspace=eng.workspace)
-        if self.ddp is not None:
-            K.dualreg_loss_finish(eng.workspace, pix, sums, None, pix_global, 0.0, 0.0, 0.0, None)
-            self.ddp.all_reduce_loss_stats(sums)
-            K.dualreg_loss_finish(None, pix, sums, stats, pix_global, *w, terms)
-            self.ddp.begin_backward()
-        else:
-            K.dualreg_loss_finish(eng.workspace, pix, sums, stats, pix_global, *w, terms)
+        self._finish_loss(K.dualreg_loss_finish, eng.workspace, pix, sums, (stats,), pix_global, w, terms)
         eng.backward_net(dcoarse, doffset)
         if self.ddp is not None:
             self.ddp.finish()

@@ -45,10 +45,11 @@ class FlatParamEngine:
     # packed-weight buffers.  Those buffers are therefore never freed when another input shape comes along (a ragged
     # last validation batch between two graph replays): every shape key owns its own buffer set, kept alive in
     # ``_shape_sets`` and swapped in O(1).  Everything an engine assigns in its _prepare*() is per-shape state;
-    # the names below are the shape-independent ones.
+    # the names below are the shape-independent ones: configuration, the flat buffers, and the pass counters
+    # (``fwd_serial``, ``autograd_pass``), which count passes of the engine, not of a shape.
     _SHAPE_INDEPENDENT = frozenset((
-        'module', 'dtype', 'requested_dtype', 'mx8', 'model_name', 'depth_norm', 'n', 'levels', '_build', '_saved', 'flat_p', 'flat_g', 'flat_w16',
-        'param_meta', 'total', 'offset', 'on_grad_ready', '_shape_key', '_shape_sets', '_packed_version',
+        'module', 'dtype', 'requested_dtype', 'requested_plane', 'mx8', 'model_name', 'depth_norm', 'n', 'levels', '_build',
+        '_saved', 'flat_p', 'flat_g', 'flat_w16', 'fwd_serial', 'autograd_pass', 'param_meta', 'total', 'offset', 'on_grad_ready', '_shape_key', '_shape_sets', '_packed_version',
         'weights_dirty', 's2_fresh', 'train_offset', 'step_counter', 'dropout_seed', 'final_act', 'vae', 'vae_seed',
         'vae_draws', 'eps_in', 'g_kl', 'loss_acc', 'unused_params'))
     MAX_SHAPE_SETS = 4

@@ -185,6 +185,19 @@ class OptimTail(GraphedStep):
         self.state[1] = 1.0 - self.betas[0] ** step
         self.state[2] = 1.0 - self.betas[1] ** step
 
+    def _finish_loss(self, finish, workspace, pix, sums, stats, pix_global, weights, terms):
+        """Second half of a fused loss pass (``finish`` = adn_*_loss_finish): block sums in ``workspace`` -> ``sums`` ->
+        weighted ``terms``.  ``stats`` is the tuple of statistics the family's finish takes in front of the global pixel
+        count (may be empty).  Under the data-parallel reducer the sums are finished locally, all-reduced and finished
+        again (one global-batch loss, as under DataParallel), and the reducer is armed for the backward pass."""
+        if self.ddp is None:
+            finish(workspace, pix, sums, *stats, pix_global, *weights, terms)
+            return
+        finish(workspace, pix, sums, *(None,) * len(stats), pix_global, *(0.0,) * len(weights), None)
+        self.ddp.all_reduce_loss_stats(sums)
+        finish(None, pix, sums, *stats, pix_global, *weights, terms)
+        self.ddp.begin_backward()
+
     def _apply(self, fused_norm=False):
         """Clip and step flat_p[offset:] from flat_g[offset:].  The total norm comes from what the weight-gradient
         kernels left in the engine's ``sq_all`` (``fused_norm``), from the reducer's per-bucket sums, or from a pass

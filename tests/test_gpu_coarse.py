@@ -417,3 +417,25 @@ def test_train_coarse_depth_synthetic_run_writes_a_checkpoint(tmp_path, monkeypa
     np.testing.assert_array_equal(ck['bin_centers'].numpy(), z['centers/linear'])
     np.testing.assert_array_equal(ck['bin_edges'].numpy(), z['edges/linear'])
     np.testing.assert_array_equal(ck['state_dict']['bin_centers'].numpy(), z['centers/linear'])
+
+
+def test_stale_backward_is_refused_across_shapes():
+    """The pass counters belong to the engine, not to a shape's buffer set: a training forward at shape A, one at B and
+    one at A again leave B's autograd context stale, and its backward is refused before any kernel runs.  (With the
+    counters parked per shape, the third forward restored A's count 1 and raised it to 2 = the stamp of B's context.)"""
+    m = _model(torch.bfloat16, nb=16, base=16, S=32)
+    eng = m.engine()
+    g = torch.Generator().manual_seed(4)
+    xA = torch.rand(1, 2, 32, 32, generator=g).to(DEV)
+    xB = torch.rand(1, 2, 64, 32, generator=g).to(DEV)        # only the width is tied to output_size
+    serials = [eng.fwd_serial]
+    m(xA)
+    serials.append(eng.fwd_serial)
+    _, dB = m(xB)
+    serials.append(eng.fwd_serial)
+    m(xA)
+    serials.append(eng.fwd_serial)
+    assert eng.autograd_pass == 3
+    assert all(b > a for a, b in zip(serials, serials[1:])), serials
+    with pytest.raises(RuntimeError, match='overwritten'):
+        dB.sum().backward()
