@@ -1,5 +1,5 @@
 // Epilogue of the implicit-GEMM family, shared by the fused MFMA path (8 channels per thread,
-// 16-byte accesses) and the split-K / generic reduce path (1 element per call).
+// 16-byte accesses) and the split-K / generic reduce path (1 element per call, or its arithmetic on 8 registers).
 #pragma once
 #include "adn_common.h"
 
@@ -214,5 +214,158 @@ __device__ __forceinline__ void epi_bwd_pre8(const AdnEpiSeg& sg, const EpiCols&
       s1[e] += g[e];
       s2[e] += g[e] * ((z[e] - c.a[e]) * c.b[e]);
     }
+  }
+}
+
+// ---- epi_scalar on 8 registers (the vector form of the split-K / direct reduce kernel) -------------
+// The arithmetic of epi_scalar, element for element and bit for bit -- NOT that of epi_vec8, which adds a zero bias
+// (-0 becomes +0) and folds shift + bias ahead of the multiply-add in ACT.  epi_scalar compiles without a single fused
+// multiply-add: its mul -> add pairs sit in different basic blocks, and the two statistics adds are paired into one
+// v_pk_add_f32.  In straight-line code over 8 registers the compiler would contract them (-ffp-contract=fast), so every
+// product that feeds an add goes through epi_unfused().
+__device__ __forceinline__ float epi_unfused(float x) {
+  asm("" : "+v"(x));
+  return x;
+}
+
+// The bf16 / f32 operand chunks of 8 channels, requested ahead of the arithmetic and unpacked behind it.
+template <typename T>
+struct EpiRaw8 {
+  u32x4_t c[sizeof(T) == 2 ? 1 : 2];
+};
+template <typename T>
+__device__ __forceinline__ void raw8_load(const void* base, int64_t idx, EpiRaw8<T>& r) {
+  const u32x4_t* p = reinterpret_cast<const u32x4_t*>(reinterpret_cast<const T*>(base) + idx);
+  r.c[0] = p[0];
+  if constexpr (sizeof(T) == 4) r.c[1] = p[1];
+}
+template <typename T>
+__device__ __forceinline__ void raw8_unpack(const EpiRaw8<T>& r, float* f) {
+  Chunk<T>::unpack(r.c[0], f);
+  if constexpr (sizeof(T) == 4) Chunk<T>::unpack(r.c[1], f + 4);
+}
+
+// Per-channel vectors of the 8 channels, as epi_scalar reads them (a: scale / mean, b: shift / istd, c: bias)
+struct EpiVecs8 {
+  float a[8], b[8], c[8];
+};
+template <int EPI>
+__device__ __forceinline__ void epi_scalar8_vecs(const AdnEpiSeg& sg, int nl, EpiVecs8& k) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    if constexpr (EPI == ADN_EPI_ACT) {
+      if (sg.scale) k.a[e] = sg.scale[nl + e];
+      if (sg.shift) k.b[e] = sg.shift[nl + e];
+    } else if constexpr (EPI == ADN_EPI_BWD) {
+      if (sg.partials) {
+        k.a[e] = sg.mean[nl + e];
+        k.b[e] = sg.istd[nl + e];
+      }
+    } else if constexpr (EPI == ADN_EPI_ADD) {
+      if (sg.scale) k.a[e] = sg.final_act ? sg.scale[0] : sg.scale[nl + e];
+    }
+    if constexpr (EPI != ADN_EPI_RAW && EPI != ADN_EPI_BWD) {
+      if (sg.bias) k.c[e] = sg.bias[nl + e];
+    }
+  }
+}
+
+// The tensors an element's epilogue reads besides the GEMM result: ref (BWD, ADD), old out0 (accumulate), z (BWD stats)
+template <typename T>
+struct EpiOps8 {
+  EpiRaw8<T> ref, old, z;
+};
+template <typename T, int EPI>
+__device__ __forceinline__ void epi_scalar8_request(const AdnEpiSeg& sg, int64_t op, int nl, EpiOps8<T>& o) {
+  const int64_t idx = op * sg.channels + nl;
+  if constexpr (EPI == ADN_EPI_BWD) {
+    raw8_load<T>(sg.ref, idx, o.ref);
+    if (sg.accumulate) raw8_load<T>(sg.out0, idx, o.old);
+    if (sg.partials) raw8_load<T>(sg.z, idx, o.z);
+  } else if constexpr (EPI == ADN_EPI_ADD) {
+    if (sg.ref) raw8_load<T>(sg.ref, idx, o.ref);
+    if (sg.accumulate) raw8_load<T>(sg.out0, idx, o.old);
+  }
+}
+
+// v: the GEMM results of output pixel `op`, channels nl .. nl+7 of segment `sg`.  t1 / t2: the element's statistics terms
+// (Z_STATS: t1 = z; BWD: t1 = g, t2 = (z - mean) * istd); the caller folds them in row order:
+// s1 += t1, s2 += epi_unfused(t1 * t1) resp. epi_unfused(t1 * t2).
+template <typename T, int EPI>
+__device__ __forceinline__ void epi_scalar8(const AdnEpiSeg& sg, const EpiVecs8& k, const EpiOps8<T>& o, int64_t op, int nl,
+                                            const float* v, float* t1, float* t2) {
+  const int64_t idx = op * sg.channels + nl;
+  if constexpr (EPI == ADN_EPI_RAW) {
+    store8<float>(sg.out0, idx, v);
+  } else if constexpr (EPI == ADN_EPI_Z_STATS) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) t1[e] = sg.bias ? v[e] + k.c[e] : v[e];
+    store8<T>(sg.out0, idx, t1);
+  } else if constexpr (EPI == ADN_EPI_ACT) {
+    float y[8], w[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      y[e] = v[e];
+      if (sg.scale) y[e] = epi_unfused(y[e] * k.a[e]);
+      if (sg.shift) y[e] += k.b[e];
+      if (sg.bias) y[e] += k.c[e];
+    }
+    if (sg.out0) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) w[e] = y[e] > 0.f ? y[e] : y[e] * sg.slope;
+      store8<T>(sg.out0, idx, w);
+    }
+    if (sg.out1) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) w[e] = fmaxf(y[e], 0.f);
+      store8<T>(sg.out1, idx, w);
+    }
+  } else if constexpr (EPI == ADN_EPI_BWD) {
+    float r[8], g[8];
+    raw8_unpack<T>(o.ref, r);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) g[e] = epi_unfused(v[e] * (r[e] > 0.f ? 1.0f : sg.slope));
+    if (sg.accumulate) {
+      float old[8];
+      raw8_unpack<T>(o.old, old);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) g[e] += old[e];
+    }
+    store8<T>(sg.out0, idx, g);
+    if (sg.partials) {
+      float z[8];
+      raw8_unpack<T>(o.z, z);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        t1[e] = g[e];
+        t2[e] = (z[e] - k.a[e]) * k.b[e];
+      }
+    }
+  } else if constexpr (EPI == ADN_EPI_ADD) {
+    float g[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      g[e] = v[e];
+      if (sg.bias) g[e] += k.c[e];
+      if (sg.scale) g[e] = epi_unfused(g[e] * k.a[e]);
+    }
+    if (sg.ref) {
+      float r[8];
+      raw8_unpack<T>(o.ref, r);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) g[e] += r[e];
+    }
+    if (sg.accumulate) {
+      float old[8];
+      raw8_unpack<T>(o.old, old);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) g[e] += old[e];
+    }
+    store8<T>(sg.out0, idx, g);
+  } else {  // ADN_EPI_FINAL
+    float y[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) y[e] = adn_final_act(sg.bias ? v[e] + k.c[e] : v[e], sg.final_act);
+    store8<float>(sg.out0, idx, y);
   }
 }

@@ -15,6 +15,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <mutex>
 
@@ -29,7 +30,7 @@ namespace {
 //                                               descriptor (every load dropped, zeros in LDS; wrong results)
 //   ADN_IGEMM_SKIP                              same builds: bit 0 / 1 = the operand's LDS-DMA is not issued at all
 struct Tune {
-  int bm = 0, bn = 0, ns = 0, noa = 0, nob = 0, skip = 0, patch = 1, tall = 1, pair = 1, tinycap = 4, bn_t2 = 0, onepx = 1, ring = 1, ring_sched = 1, ring_epi = 0, ring_geom = -1, ring_hs = 0, ring64n = 1;
+  int bm = 0, bn = 0, ns = 0, noa = 0, nob = 0, skip = 0, patch = 1, tall = 1, pair = 1, tinycap = 4, bn_t2 = 0, onepx = 1, ring = 1, ring_sched = 1, ring_epi = 0, ring_geom = -1, ring_hs = 0, ring64n = 1, reduce_vec = 1;
 };
 const Tune& tune() {
   static Tune t;
@@ -55,6 +56,7 @@ const Tune& tune() {
     if (const char* e = getenv("ADN_IGEMM_RING_GEOM")) t.ring_geom = atoi(e);    // A/B: ring kernel only for this geometry (0 | 1)
     if (const char* e = getenv("ADN_IGEMM_RING_HS")) t.ring_hs = atoi(e);        // A/B: ring kernel only at this small-grid height
     if (const char* e = getenv("ADN_IGEMM_RING_N64")) t.ring64n = atoi(e);       // A/B: 64-column layers on the ring kernel too
+    if (const char* e = getenv("ADN_IGEMM_REDUCE")) t.reduce_vec = strcmp(e, "scalar") != 0;      // A/B: "scalar" = igemm_reduce_kernel everywhere
   });
   return t;
 }
@@ -910,6 +912,107 @@ __global__ __launch_bounds__(256) void igemm_reduce_kernel(KParams p, int64_t mo
   }
 }
 
+// ---- the same reduce with 16-byte accesses and every row of the block in flight ----
+// Same grid, same rb rows x 256 channels per block, same bits as igemm_reduce_kernel; what changes is who does what.
+// Thread = 8 consecutive channels (column group cg = tid % 32) of ONE row (tid / 32; the rows of a block go to different
+// threads, a block has 32 * min(rb, 8) threads and walks rb > 8 in passes).  Per row a thread first requests the BWD / ADD
+// operand chunks, then walks the slabs in groups of up to 8 (two f32x4 loads per slab, all of a group issued before its
+// first add, added in split order), and runs epi_scalar's arithmetic on its 8 registers (epi_scalar8).  The statistics keep
+// their order: every row leaves its terms in LDS (terms[2][rb][256]) and one thread per channel folds them from 0 in
+// increasing row order, with the rounding epi_scalar has (the product is rounded on its own, see epi_unfused).
+template <int G>
+__device__ __forceinline__ void slab_group_add(const float* src, int64_t slab_stride, float* v) {
+  f32x4_t x[G][2];
+#pragma unroll
+  for (int j = 0; j < G; ++j) {
+    const f32x4_t* q = reinterpret_cast<const f32x4_t*>(src + j * slab_stride);
+    x[j][0] = q[0];
+    x[j][1] = q[1];
+  }
+#pragma unroll
+  for (int j = 0; j < G; ++j) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] += x[j][e >> 2][e & 3];
+  }
+}
+
+template <typename T, int EPI>
+__global__ __launch_bounds__(256) void igemm_reduce_vec_kernel(KParams p, int64_t mout, int rb) {
+  constexpr bool STATS = EPI == ADN_EPI_Z_STATS || EPI == ADN_EPI_BWD;
+  // slabs per group: 8 (64 VGPRs of slab data) where the epilogue holds little else; 4 for the epilogues that also hold
+  // operand chunks and per-channel vectors across the walk (with 8 they need 146 ... 184 VGPRs: under 4 waves per SIMD)
+  // (f32 BWD holds twice the operand chunks: 2)
+  constexpr int GMAX = (EPI == ADN_EPI_BWD && sizeof(T) == 4) ? 2
+                       : (EPI == ADN_EPI_ACT || EPI == ADN_EPI_BWD || EPI == ADN_EPI_ADD) ? 4 : 8;
+  extern __shared__ float reduce_terms[];      // STATS: [EPI == BWD ? 2 : 1][rb][256]
+  const int64_t row0 = (int64_t)blockIdx.x * rb;
+  const int64_t slab_stride = mout * p.N;
+  const int cg = threadIdx.x & 31, rstep = blockDim.x >> 5;
+  const int n = blockIdx.y * 256 + cg * 8;
+  if (n < p.N) {
+    const bool in0 = n < p.seg[0].channels;
+    const AdnEpiSeg& sg = in0 ? p.seg[0] : p.seg[1];
+    const int nl = in0 ? n : n - p.seg[0].channels;
+    EpiVecs8 k;
+    epi_scalar8_vecs<EPI>(sg, nl, k);
+    for (int r = threadIdx.x >> 5; r < rb; r += rstep) {
+      const int64_t op = row0 + r;
+      if (op >= mout) break;
+      EpiOps8<T> ops;
+      epi_scalar8_request<T, EPI>(sg, op, nl, ops);
+      const float* src = p.slab + op * p.N + n;
+      float v[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = 0.f;
+      int s = 0;
+      if constexpr (GMAX == 8) {
+        for (; s + 8 <= p.nsplit; s += 8) slab_group_add<8>(src + s * slab_stride, slab_stride, v);
+      }
+      if constexpr (GMAX >= 4) {
+        for (; s + 4 <= p.nsplit; s += 4) slab_group_add<4>(src + s * slab_stride, slab_stride, v);
+      }
+      for (; s + 2 <= p.nsplit; s += 2) slab_group_add<2>(src + s * slab_stride, slab_stride, v);
+      if (s < p.nsplit) slab_group_add<1>(src + s * slab_stride, slab_stride, v);
+      float t1[8], t2[8];
+      epi_scalar8<T, EPI>(sg, k, ops, op, nl, v, t1, t2);
+      if constexpr (STATS) {
+        if (sg.partials) {
+          f32x4_t* d1 = reinterpret_cast<f32x4_t*>(reduce_terms + r * 256 + cg * 8);
+          d1[0] = f32x4_t{t1[0], t1[1], t1[2], t1[3]};
+          d1[1] = f32x4_t{t1[4], t1[5], t1[6], t1[7]};
+          if constexpr (EPI == ADN_EPI_BWD) {
+            f32x4_t* d2 = reinterpret_cast<f32x4_t*>(reduce_terms + (rb + r) * 256 + cg * 8);
+            d2[0] = f32x4_t{t2[0], t2[1], t2[2], t2[3]};
+            d2[1] = f32x4_t{t2[4], t2[5], t2[6], t2[7]};
+          }
+        }
+      }
+    }
+  }
+  if constexpr (STATS) {
+    __syncthreads();
+    const int64_t left = mout - row0;
+    const int rows = left < rb ? (int)left : rb;
+    for (int c = threadIdx.x; c < 256; c += blockDim.x) {
+      const int nc = blockIdx.y * 256 + c;
+      if (nc >= p.N) break;
+      const bool in0 = nc < p.seg[0].channels;
+      const AdnEpiSeg& sg = in0 ? p.seg[0] : p.seg[1];
+      if (!sg.partials) continue;
+      const int nl = in0 ? nc : nc - p.seg[0].channels;
+      float s1 = 0.f, s2 = 0.f;
+      for (int r = 0; r < rows; ++r) {
+        const float a = reduce_terms[r * 256 + c];
+        const float b = EPI == ADN_EPI_BWD ? reduce_terms[(rb + r) * 256 + c] : a;
+        s1 += a;
+        s2 += epi_unfused(a * b);
+      }
+      sg.partials[((int64_t)blockIdx.x * 2 + 0) * sg.channels + nl] = s1;
+      sg.partials[((int64_t)blockIdx.x * 2 + 1) * sg.channels + nl] = s2;
+    }
+  }
+}
+
 inline int reduce_rows(int64_t mout, int N) {
   const int64_t cb = adn_cdiv(N, 256);
   int64_t rb = mout * cb / 1024;
@@ -1221,8 +1324,34 @@ int run(const AdnIgemmDesc* d, const Plan& pl, hipStream_t st) {
   kp.rec_b = tune().nob ? 0u : 0x7ffffff0u;
   kp.skip = tune().skip;
   auto reduce = [&]() {
-    hipLaunchKernelGGL((igemm_reduce_kernel<T>), dim3((unsigned)adn_cdiv(pl.mout, pl.rb), (unsigned)adn_cdiv(d->N, 256)),
-                       dim3(256), 0, st, kp, pl.mout, pl.rb);
+    const dim3 grid((unsigned)adn_cdiv(pl.mout, pl.rb), (unsigned)adn_cdiv(d->N, 256));
+    // vector form: every 8-channel group inside one segment and every chunk 16-byte aligned, the statistics terms of the
+    // block's rows within 64 KB of LDS; anything else runs the scalar kernel
+    const bool stats = d->epi == ADN_EPI_Z_STATS || d->epi == ADN_EPI_BWD;
+    const size_t lds = stats ? (size_t)pl.rb * 256 * sizeof(float) * (d->epi == ADN_EPI_BWD ? 2 : 1) : 0;
+    auto aligned16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    bool vec = tune().reduce_vec != 0 && d->N % 8 == 0 && lds <= 65536 && aligned16(kp.slab);
+    for (int s = 0; s < 2; ++s) {
+      const AdnEpiSeg& g = d->seg[s];
+      if (g.channels == 0) continue;
+      vec = vec && g.channels % 8 == 0 && aligned16(g.out0) && aligned16(g.out1) && aligned16(g.ref) && aligned16(g.z);
+    }
+    if (!vec) {
+      hipLaunchKernelGGL((igemm_reduce_kernel<T>), grid, dim3(256), 0, st, kp, pl.mout, pl.rb);
+      return;
+    }
+    const dim3 block(pl.rb >= 8 ? 256 : (pl.rb > 2 ? 32 * pl.rb : 64));
+    switch (d->epi) {
+#define ADN_REDUCE_VEC(E) \
+  case E: hipLaunchKernelGGL((igemm_reduce_vec_kernel<T, E>), grid, block, lds, st, kp, pl.mout, pl.rb); break;
+      ADN_REDUCE_VEC(ADN_EPI_RAW)
+      ADN_REDUCE_VEC(ADN_EPI_Z_STATS)
+      ADN_REDUCE_VEC(ADN_EPI_ACT)
+      ADN_REDUCE_VEC(ADN_EPI_BWD)
+      ADN_REDUCE_VEC(ADN_EPI_FINAL)
+      ADN_REDUCE_VEC(ADN_EPI_ADD)
+#undef ADN_REDUCE_VEC
+    }
   };
   switch (pl.kind) {
     case Kind::Ring:
