@@ -8,7 +8,7 @@
 //   distill_pix_*  final = clamp(base + residual), masked L1 / MSE-to-teacher / |residual| terms and their gradients
 //   featcos_*      1 - mean cosine similarity of spatially normalised features, per encoder level
 //   distill_small  KL of the temperature-softened mean logits, bin-centre MSE, assembly of the total loss
-#include "adn_common.h"
+#include "loss_tail.h"
 #include "epilogue.h"
 
 namespace {
@@ -371,41 +371,29 @@ __global__ __launch_bounds__(256) void bins_bwd_kernel(const void* logits, const
 __global__ __launch_bounds__(256) void distill_pix_stats_kernel(const float* base, const float* resid, const float* gt,
                                                                 const float* teacher, int64_t n, float maxd, float* final_out,
                                                                 double* partial) {
-  double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
     const float f = fminf(fmaxf(base[e] + resid[e], 0.f), maxd);
     final_out[e] = f;
     if (gt[e] > 0.f) {
-      s0 += 1.0;
-      s1 += (double)fabsf(f - gt[e]);
+      s[0] += 1.0;
+      s[1] += (double)fabsf(f - gt[e]);
       if (teacher) {
         const float d = f - teacher[e];
-        s2 += (double)(d * d);
+        s[2] += (double)(d * d);
       }
-      s3 += (double)fabsf(resid[e]);
+      s[3] += (double)fabsf(resid[e]);
     }
   }
-  __shared__ double sm[4][4];
-  s0 = wave_sum_d(s0); s1 = wave_sum_d(s1); s2 = wave_sum_d(s2); s3 = wave_sum_d(s3);
-  if ((threadIdx.x & 63) == 0) {
-    const int w = threadIdx.x >> 6;
-    sm[0][w] = s0; sm[1][w] = s1; sm[2][w] = s2; sm[3][w] = s3;
-  }
-  __syncthreads();
-  if (threadIdx.x < 4)
-    partial[(int64_t)blockIdx.x * 4 + threadIdx.x] = sm[threadIdx.x][0] + sm[threadIdx.x][1] + sm[threadIdx.x][2] + sm[threadIdx.x][3];
+  block_partial_row(s, partial + (int64_t)blockIdx.x * 4);
 }
 
 __global__ __launch_bounds__(64) void sum4_kernel(const double* partial, int nbk, double* stats) {
-  for (int q = 0; q < 4; ++q) {
-    double s = 0.0;
-    for (int r = threadIdx.x; r < nbk; r += 64) s += partial[(int64_t)r * 4 + q];
-    s = wave_sum_d(s);
-    if (threadIdx.x == 0) stats[q] = s;
-  }
+  double s[4];
+  sum_partial_rows_wave(partial, nbk, s);
+  if (threadIdx.x == 0)
+    for (int q = 0; q < 4; ++q) stats[q] = s[q];
 }
-
-__device__ __forceinline__ float sgnf(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
 
 __global__ __launch_bounds__(256) void distill_pix_grad_kernel(const float* base, const float* resid, const float* gt,
                                                                const float* teacher, int64_t n, float maxd,
@@ -417,10 +405,10 @@ __global__ __launch_bounds__(256) void distill_pix_grad_kernel(const float* base
     const float f = fminf(fmaxf(s, 0.f), maxd);
     float db = 0.f, dr = 0.f;
     if (gt[e] > 0.f) {
-      float df = lt * sgnf(f - gt[e]) * invn;
+      float df = lt * adn_sgn(f - gt[e]) * invn;
       if (teacher) df += lr * 2.f * (f - teacher[e]) * invn;
       if (s >= 0.f && s <= maxd) db = df;                  // torch.clamp passes the gradient on [min, max]
-      dr = db + ls * sgnf(resid[e]) * invn;
+      dr = db + ls * adn_sgn(resid[e]) * invn;
     }
     dbase[e] = db;
     dres[e] = dr;
@@ -518,12 +506,7 @@ __global__ __launch_bounds__(256) void distill_small_kernel(SmallParams p) {
   }
 }
 
-inline unsigned blocks_for(int64_t n) {
-  int64_t b = adn_cdiv(n, 256);
-  if (b > 4096) b = 4096;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
+inline unsigned blocks_for(int64_t n) { return adn_grid_blocks(n, 256, 4096); }
 inline int pool_parts(int HW) {
   int P = (int)adn_cdiv(HW, 64);
   if (P > 64) P = 64;
@@ -657,9 +640,7 @@ extern "C" int adn_distill_pix_stats(const float* base, const float* resid, cons
   ADN_CHECK_ARG(base && resid && gt && final_out && stats && n > 0, "adn_distill_pix_stats: bad arguments");
   ADN_CHECK_ARG(workspace && workspace_bytes >= 1024 * 4 * 8, "adn_distill_pix_stats: workspace too small (32 KiB)");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  int nbk = (int)adn_cdiv(n, 2048);
-  if (nbk > 1024) nbk = 1024;
-  if (nbk < 1) nbk = 1;
+  const int nbk = adn_grid_blocks(n, 2048, 1024);
   double* part = reinterpret_cast<double*>(workspace);
   hipLaunchKernelGGL(distill_pix_stats_kernel, dim3(nbk), dim3(256), 0, st, base, resid, gt, teacher, n, max_depth,
                      final_out, part);

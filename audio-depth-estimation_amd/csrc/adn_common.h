@@ -131,7 +131,17 @@ __device__ __forceinline__ void mma_tile(const u32x4_t& a, const u32x4_t& b, f32
   }
 }
 
+// sign with sgn(0) = 0: torch's abs backward
+__device__ __forceinline__ float adn_sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
+
 static inline int64_t adn_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// grid of a grid-stride kernel: one block per per_block units of work, clamped to [1, cap]
+static inline int adn_grid_blocks(int64_t n, int64_t per_block, int64_t cap) {
+  int64_t b = adn_cdiv(n, per_block);
+  if (b > cap) b = cap;
+  if (b < 1) b = 1;
+  return (int)b;
+}
 // Raise a kernel's dynamic-LDS limit exactly once per instantiation.  Launch functions run concurrently on the
 // caller's threads (backward is driven from autograd threads): a plain static flag would be a data race.
 #include <mutex>

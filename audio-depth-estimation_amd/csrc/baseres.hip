@@ -6,7 +6,7 @@
 //   grad      final = clamp(base + residual, 0, max_depth): routes d loss / d final (from the masked recon loss kernels
 //             of loss_optim.hip) to base and residual and adds the structural and sparsity terms
 //   total     loss value = recon + lambda_base * mean|base - struct| + lambda_sparse * mean|residual|
-#include "adn_common.h"
+#include "loss_tail.h"
 
 namespace {
 
@@ -60,34 +60,22 @@ __global__ __launch_bounds__(256) void lowpass_cols_kernel(const float* hs, int 
 
 __global__ __launch_bounds__(256) void baseres_stats_kernel(const float* base, const float* resid, const float* strct,
                                                             const float* gt, int64_t n, double* partial) {
-  double s0 = 0, s1 = 0, s2 = 0;
+  double s[3] = {0.0, 0.0, 0.0};
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
     if (gt[e] > 0.f) {
-      s0 += 1.0;
-      s1 += (double)fabsf(base[e] - strct[e]);
-      s2 += (double)fabsf(resid[e]);
+      s[0] += 1.0;
+      s[1] += (double)fabsf(base[e] - strct[e]);
+      s[2] += (double)fabsf(resid[e]);
     }
   }
-  __shared__ double sm[3][4];
-  s0 = wave_sum_d(s0); s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
-  if ((threadIdx.x & 63) == 0) {
-    const int w = threadIdx.x >> 6;
-    sm[0][w] = s0; sm[1][w] = s1; sm[2][w] = s2;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3)
-    partial[(int64_t)blockIdx.x * 3 + threadIdx.x] = sm[threadIdx.x][0] + sm[threadIdx.x][1] + sm[threadIdx.x][2] + sm[threadIdx.x][3];
+  block_partial_row(s, partial + (int64_t)blockIdx.x * 3);
 }
 
 // stats[0..2] = sums; terms f32[4] = recon, base, sparse, total
 __global__ __launch_bounds__(64) void baseres_total_kernel(const double* partial, int nbk, const float* recon, float lrecon,
                                                            float lbase, float lsparse, double* stats, float* terms) {
   double s[3];
-  for (int q = 0; q < 3; ++q) {
-    double a = 0.0;
-    for (int r = threadIdx.x; r < nbk; r += 64) a += partial[(int64_t)r * 3 + q];
-    s[q] = wave_sum_d(a);
-  }
+  sum_partial_rows_wave(partial, nbk, s);
   if (threadIdx.x == 0) {
     stats[0] = s[0]; stats[1] = s[1]; stats[2] = s[2];
     const float lb = s[0] > 0 ? (float)(s[1] / s[0]) : NAN, ls = s[0] > 0 ? (float)(s[2] / s[0]) : NAN;
@@ -99,8 +87,6 @@ __global__ __launch_bounds__(64) void baseres_total_kernel(const double* partial
   }
 }
 
-__device__ __forceinline__ float sgn3(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
-
 __global__ __launch_bounds__(256) void baseres_grad_kernel(const float* base, const float* resid, const float* strct,
                                                            const float* gt, const float* gfinal, int64_t n, float maxd,
                                                            const double* stats, float lbase, float lsparse, float* dbase,
@@ -111,8 +97,8 @@ __global__ __launch_bounds__(256) void baseres_grad_kernel(const float* base, co
     const float gf = (s >= 0.f && s <= maxd) ? gfinal[e] : 0.f;       // clamp passes the gradient on [0, max_depth]
     float db = gf, dr = gf;
     if (gt[e] > 0.f) {
-      db += lbase * sgn3(base[e] - strct[e]) * invn;
-      dr += lsparse * sgn3(resid[e]) * invn;
+      db += lbase * adn_sgn(base[e] - strct[e]) * invn;
+      dr += lsparse * adn_sgn(resid[e]) * invn;
     }
     dbase[e] = db;
     dres[e] = dr;
@@ -124,12 +110,7 @@ __global__ __launch_bounds__(256) void clamp_add_kernel(const float* a, const fl
     out[e] = fminf(fmaxf(a[e] + b[e], 0.f), maxd);
 }
 
-inline unsigned blocks_for(int64_t n) {
-  int64_t b = adn_cdiv(n, 256);
-  if (b > 4096) b = 4096;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
+inline unsigned blocks_for(int64_t n) { return adn_grid_blocks(n, 256, 4096); }
 
 }  // namespace
 
@@ -167,9 +148,7 @@ extern "C" int adn_baseres_stats(const float* base, const float* resid, const fl
   ADN_CHECK_ARG(base && resid && strct && gt && recon && stats && terms && n > 0, "adn_baseres_stats: bad arguments");
   ADN_CHECK_ARG(workspace && workspace_bytes >= 1024 * 3 * 8, "adn_baseres_stats: workspace too small (24 KiB)");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  int nbk = (int)adn_cdiv(n, 2048);
-  if (nbk > 1024) nbk = 1024;
-  if (nbk < 1) nbk = 1;
+  const int nbk = adn_grid_blocks(n, 2048, 1024);
   double* part = reinterpret_cast<double*>(workspace);
   hipLaunchKernelGGL(baseres_stats_kernel, dim3(nbk), dim3(256), 0, st, base, resid, strct, gt, n, part);
   ADN_CHECK_LAUNCH();

@@ -5,12 +5,10 @@
 //   coarse_loss      ONE pass over the logits: softmax expectation (depth), optional argmax, classification loss
 //                    (soft CE / focal / plain CE) + masked L1 of the expectation, and the gradient of their weighted sum
 //   coarse_finish    per-block f64 partials -> sums -> (ce, regression, total)
-#include "adn_common.h"
+#include "loss_tail.h"
 
 namespace {
 
-constexpr int kMaxNb = 512;          // 8 x 64 lanes of one wave (generic kernel) / 64 lanes x one 16-byte chunk (vector kernel)
-constexpr int kMaxBlocks = 2048;
 constexpr int kTargetBlocks = 1024;
 
 struct CoarseP {
@@ -20,8 +18,6 @@ struct CoarseP {
   int nb, ld, ce_mode;
   float inv_2s2, gamma, ce_coef, reg_weight;      // 1 / (2 sigma^2);  ce_coef = ce_weight / global pixel count
 };
-
-__device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
 
 // What one pixel contributes once its reductions are known.  se = sum exp(x - max), sc = sum exp(x - max) c,
 // S = sum of the unnormalised soft labels g_k, A = sum g_k (x_k - max)  (modes 1, 2: A = x_t - max).
@@ -56,7 +52,7 @@ __device__ __forceinline__ PixTerms pixel_terms(const CoarseP& p, float se, floa
   if (gtv > 0.f) {
     const float d = t.depth - gtv;
     t.l1 = fabsf(d);
-    t.r = p.reg_weight * sgn(d) * inv_nv;
+    t.r = p.reg_weight * adn_sgn(d) * inv_nv;
   }
   return t;
 }
@@ -66,190 +62,75 @@ __device__ __forceinline__ float grad_elem(const CoarseP& p, const PixTerms& t, 
   return p.ce_coef * ce + t.r * pk * (ck - t.depth);
 }
 
-__device__ __forceinline__ void block_partials(double a, double b, double* out) {      // 256 threads
-  __shared__ double sm[2][4];
-  a = wave_sum_d(a);
-  b = wave_sum_d(b);
-  if ((threadIdx.x & 63) == 0) {
-    sm[0][threadIdx.x >> 6] = a;
-    sm[1][threadIdx.x >> 6] = b;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) out[threadIdx.x] = sm[threadIdx.x][0] + sm[threadIdx.x][1] + sm[threadIdx.x][2] + sm[threadIdx.x][3];
-}
-
-// bf16, ld == nb = 8 LPP, LPP a power of two <= 64 (bins_fwd_vec_kernel's layout): a pixel's bins are LPP lanes x one 16-byte
-// load each, 64 / LPP pixels per wave-iteration, reductions across those lanes only; the gradient leaves as one 16-byte store
-template <int LPP>
-__global__ __launch_bounds__(256) void coarse_loss_vec_kernel(CoarseP p) {
-  constexpr int NB = LPP * 8, PPW = 64 / LPP;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int li = lane % LPP, pw = lane / LPP;
-  const uint16_t* lg = reinterpret_cast<const uint16_t*>(p.logits);
-  uint16_t* dl = reinterpret_cast<uint16_t*>(p.dlogits);
+// one body over either layout of loss_tail.h (VecRow<LPP>: bins_fwd_vec_kernel's layout; WaveRow<T>)
+template <typename Row>
+__global__ __launch_bounds__(256) void coarse_loss_kernel(CoarseP p) {
+  constexpr int U = Row::U;
+  const Row row(p.nb, p.ld);
   const bool have_loss = p.bins != nullptr;
-  float cv[8];
+  float cv[U];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) cv[k] = p.centers[li * 8 + k];
+  for (int u = 0; u < U; ++u) cv[u] = row.has(u) ? p.centers[row.bin(u)] : 0.f;
   float inv_nv = 0.f;
   if (have_loss) {
     const double nv = p.n_valid[0];
     inv_nv = nv > 0.0 ? (float)(1.0 / nv) : 0.f;
   }
-  double acc_ce = 0.0, acc_l1 = 0.0;
-  for (int64_t p0 = ((int64_t)blockIdx.x * 4 + wave) * PPW; p0 < p.pixels; p0 += (int64_t)gridDim.x * 4 * PPW) {
-    const int64_t pix = p0 + pw;
-    const bool live = pix < p.pixels;
-    float d[8];
-    float mx = -INFINITY;
-    if (live) {
-      const u32x4_t c = *reinterpret_cast<const u32x4_t*>(lg + pix * NB + li * 8);
-      Chunk<uint16_t>::unpack(c, d);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) mx = fmaxf(mx, d[k]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) d[k] = 0.f;
-      mx = 0.f;
-    }
-#pragma unroll
-    for (int o = 1; o < LPP; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  double acc[2] = {0.0, 0.0};                         // ce, l1
+  for (int64_t p0 = row.first(); p0 < p.pixels; p0 += row.stride()) {
+    const int64_t pix = row.pixel(p0);
+    const bool live = row.live(pix, p.pixels);
+    float d[U];
+    const float mx = row.group_max(row.load(p.logits, pix, live, d));
     if (p.argmax) {                                   // first maximum, as torch.argmax picks it
       int cand = 0x7fffffff;
 #pragma unroll
-      for (int k = 7; k >= 0; --k)
-        if (d[k] == mx) cand = li * 8 + k;
-#pragma unroll
-      for (int o = 1; o < LPP; o <<= 1) cand = min(cand, __shfl_xor(cand, o, 64));
-      if (live && li == 0) p.argmax[pix] = cand;
+      for (int u = U - 1; u >= 0; --u)
+        if (row.has(u) && d[u] == mx) cand = row.bin(u);
+      cand = row.group_min(cand);
+      if (live && row.leader()) p.argmax[pix] = cand;
     }
     const int t = (live && have_loss) ? p.bins[pix] : 0;
-    float e[8], g[8];
-    float se = 0.f, sc = 0.f, S = 0.f, A = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      d[k] -= mx;
-      e[k] = __expf(d[k]);
-      se += e[k];
-      sc += e[k] * cv[k];
-      const int kk = li * 8 + k;
-      g[k] = 0.f;
-      if (!have_loss) continue;                       // forward only: no labels, S and A stay 0 (wave-uniform)
-      if (p.ce_mode == 0) {
-        const float dk = (float)(kk - t);
-        g[k] = __expf(-dk * dk * p.inv_2s2);
-        S += g[k];
-        A += g[k] * d[k];
-      } else {
-        A += kk == t ? d[k] : 0.f;
-      }
-    }
-#pragma unroll
-    for (int o = 1; o < LPP; o <<= 1) {
-      se += __shfl_xor(se, o, 64);
-      sc += __shfl_xor(sc, o, 64);
-      S += __shfl_xor(S, o, 64);
-      A += __shfl_xor(A, o, 64);
-    }
-    const float gtv = (live && have_loss) ? p.gt[pix] : 0.f;
-    const PixTerms pt = pixel_terms(p, se, sc, S, A, have_loss, gtv, inv_nv);
-    if (live && li == 0) {
-      p.depth[pix] = pt.depth;
-      acc_ce += (double)pt.loss;
-      acc_l1 += (double)pt.l1;
-    }
-    if (dl && live) {
-      float gr[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) gr[k] = grad_elem(p, pt, e[k] * pt.inv, g[k], li * 8 + k == t, cv[k]);
-      *reinterpret_cast<u32x4_t*>(dl + pix * NB + li * 8) = Chunk<uint16_t>::pack(gr);
-    }
-  }
-  if (have_loss) block_partials(acc_ce, acc_l1, p.partial + (int64_t)blockIdx.x * 2);
-}
-
-// every other (dtype, nb, ld): one wave per pixel, lane l holds bins l, l + 64, ... (nb <= 512), row stride ld >= nb
-template <typename T>
-__global__ __launch_bounds__(256) void coarse_loss_kernel(CoarseP p) {
-  constexpr int U = kMaxNb / 64;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const T* lg = reinterpret_cast<const T*>(p.logits);
-  T* dl = reinterpret_cast<T*>(p.dlogits);
-  const bool have_loss = p.bins != nullptr;
-  const int nb = p.nb;
-  float cv[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) cv[u] = (lane + 64 * u) < nb ? p.centers[lane + 64 * u] : 0.f;
-  float inv_nv = 0.f;
-  if (have_loss) {
-    const double nv = p.n_valid[0];
-    inv_nv = nv > 0.0 ? (float)(1.0 / nv) : 0.f;
-  }
-  double acc_ce = 0.0, acc_l1 = 0.0;
-  for (int64_t pix = (int64_t)blockIdx.x * 4 + wave; pix < p.pixels; pix += (int64_t)gridDim.x * 4) {
-    const T* row = lg + pix * p.ld;
-    float d[U], mx = -INFINITY;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int k = lane + 64 * u;
-      d[u] = k < nb ? ElemTraits<T>::load(row + k) : -INFINITY;
-      mx = fmaxf(mx, d[u]);
-    }
-    mx = wave_max(mx);
-    if (p.argmax) {
-      int cand = 0x7fffffff;
-#pragma unroll
-      for (int u = U - 1; u >= 0; --u)
-        if ((lane + 64 * u) < nb && d[u] == mx) cand = lane + 64 * u;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
-      if (lane == 0) p.argmax[pix] = cand;
-    }
-    const int t = have_loss ? p.bins[pix] : 0;
     float e[U], g[U];
     float se = 0.f, sc = 0.f, S = 0.f, A = 0.f;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const int k = lane + 64 * u;
       e[u] = g[u] = 0.f;
-      if (k < nb) {
-        d[u] -= mx;
-        e[u] = __expf(d[u]);
-        se += e[u];
-        sc += e[u] * cv[u];
-        if (!have_loss) continue;
-        if (p.ce_mode == 0) {
-          const float dk = (float)(k - t);
-          g[u] = __expf(-dk * dk * p.inv_2s2);
-          S += g[u];
-          A += g[u] * d[u];
-        } else {
-          A += k == t ? d[u] : 0.f;
-        }
+      if (!row.has(u)) continue;
+      d[u] -= mx;
+      e[u] = __expf(d[u]);
+      se += e[u];
+      sc += e[u] * cv[u];
+      const int k = row.bin(u);
+      if (!have_loss) continue;                       // forward only: no labels, S and A stay 0 (wave-uniform)
+      if (p.ce_mode == 0) {
+        const float dk = (float)(k - t);
+        g[u] = __expf(-dk * dk * p.inv_2s2);
+        S += g[u];
+        A += g[u] * d[u];
+      } else {
+        A += k == t ? d[u] : 0.f;
       }
     }
-    se = wave_sum(se);
-    sc = wave_sum(sc);
-    S = wave_sum(S);
-    A = wave_sum(A);
-    const float gtv = have_loss ? p.gt[pix] : 0.f;
+    se = row.group_sum(se);
+    sc = row.group_sum(sc);
+    S = row.group_sum(S);
+    A = row.group_sum(A);
+    const float gtv = (live && have_loss) ? p.gt[pix] : 0.f;
     const PixTerms pt = pixel_terms(p, se, sc, S, A, have_loss, gtv, inv_nv);
-    if (lane == 0) {
+    if (live && row.leader()) {
       p.depth[pix] = pt.depth;
-      acc_ce += (double)pt.loss;
-      acc_l1 += (double)pt.l1;
+      acc[0] += (double)pt.loss;
+      acc[1] += (double)pt.l1;
     }
-    if (dl) {
-      T* drow = dl + pix * p.ld;
+    if (p.dlogits && live) {
+      float gr[U];
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int k = lane + 64 * u;
-        if (k < nb) ElemTraits<T>::store(drow + k, grad_elem(p, pt, e[u] * pt.inv, g[u], k == t, cv[u]));
-      }
-      for (int k = nb + lane; k < p.ld; k += 64) ElemTraits<T>::store(drow + k, 0.f);      // the tape's padding columns
+      for (int u = 0; u < U; ++u) gr[u] = row.has(u) ? grad_elem(p, pt, e[u] * pt.inv, g[u], row.bin(u) == t, cv[u]) : 0.f;
+      row.store(p.dlogits, pix, gr);
     }
   }
-  if (have_loss) block_partials(acc_ce, acc_l1, p.partial + (int64_t)blockIdx.x * 2);
+  if (have_loss) block_partial_row(acc, p.partial + (int64_t)blockIdx.x * 2);
 }
 
 // one block: partial [rows][2] -> sums[2] (skipped when partial is NULL: the sums were all-reduced by the caller), then
@@ -257,41 +138,15 @@ __global__ __launch_bounds__(256) void coarse_loss_kernel(CoarseP p) {
 __global__ __launch_bounds__(256) void coarse_finish_kernel(const double* partial, int rows, double* sums, const double* n_valid,
                                                             double pixels_global, float ce_weight, float reg_weight,
                                                             float* terms) {
-  __shared__ double sm[2][4];
-  if (partial) {
-    double a = 0.0, b = 0.0;
-    for (int r = threadIdx.x; r < rows; r += 256) {
-      a += partial[(int64_t)r * 2];
-      b += partial[(int64_t)r * 2 + 1];
-    }
-    a = wave_sum_d(a);
-    b = wave_sum_d(b);
-    if ((threadIdx.x & 63) == 0) {
-      sm[0][threadIdx.x >> 6] = a;
-      sm[1][threadIdx.x >> 6] = b;
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    double s0, s1;
-    if (partial) {
-      s0 = sm[0][0] + sm[0][1] + sm[0][2] + sm[0][3];
-      s1 = sm[1][0] + sm[1][1] + sm[1][2] + sm[1][3];
-      sums[0] = s0;
-      sums[1] = s1;
-    } else {
-      s0 = sums[0];
-      s1 = sums[1];
-    }
-    if (terms) {
-      const double nv = n_valid[0];
-      const float ce = (float)(s0 / pixels_global);
-      const float reg = nv > 0.0 ? (float)(s1 / nv) : NAN;
-      terms[0] = ce;
-      terms[1] = reg;
-      terms[2] = ce_weight * ce + reg_weight * reg;
-    }
-  }
+  sum_partial_rows<2>(partial, rows, sums, [&](const double (&s)[2]) {
+    if (!terms) return;
+    const double nv = n_valid[0];
+    const float ce = (float)(s[0] / pixels_global);
+    const float reg = nv > 0.0 ? (float)(s[1] / nv) : NAN;
+    terms[0] = ce;
+    terms[1] = reg;
+    terms[2] = ce_weight * ce + reg_weight * reg;
+  });
 }
 
 // bins[e] = number of interior edges strictly below depth[e] (bucketize, right=False; already inside [0, nb - 1]);
@@ -299,7 +154,6 @@ __global__ __launch_bounds__(256) void coarse_finish_kernel(const double* partia
 __global__ __launch_bounds__(256) void coarse_targets_kernel(const float* depth, int64_t n, const float* edges, int ne,
                                                              int32_t* bins, double* partial) {
   __shared__ float es[kMaxNb];
-  __shared__ double sm[4];
   if (bins)
     for (int i = threadIdx.x; i < ne; i += 256) es[i] = edges[i];
   __syncthreads();
@@ -317,31 +171,18 @@ __global__ __launch_bounds__(256) void coarse_targets_kernel(const float* depth,
       bins[e] = lo;
     }
   }
-  const double c = wave_sum_d((double)cnt);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
+  double c[1] = {(double)cnt};
+  block_partial_row(c, partial + blockIdx.x);
 }
 
 __global__ __launch_bounds__(64) void coarse_count_kernel(const double* partial, int rows, double* stats) {
-  double s = 0.0;
-  for (int r = threadIdx.x; r < rows; r += 64) s += partial[r];
-  s = wave_sum_d(s);
-  if (threadIdx.x == 0) stats[0] = s;
+  double s[1];
+  sum_partial_rows_wave(partial, rows, s);
+  if (threadIdx.x == 0) stats[0] = s[0];
 }
 
-inline int loss_blocks(int64_t pixels) {
-  int64_t b = adn_cdiv(pixels, 16);
-  if (b > kMaxBlocks) b = kMaxBlocks;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-inline int target_blocks(int64_t n) {
-  int64_t b = adn_cdiv(n, 1024);
-  if (b > kTargetBlocks) b = kTargetBlocks;
-  if (b < 1) b = 1;
-  return (int)b;
-}
+inline int loss_blocks(int64_t pixels) { return adn_grid_blocks(pixels, 16, kLossBlocks); }      // both layouts
+inline int target_blocks(int64_t n) { return adn_grid_blocks(n, 1024, kTargetBlocks); }
 
 }  // namespace
 
@@ -393,20 +234,9 @@ extern "C" int adn_coarse_loss(const AdnCoarseLoss* d, void* stream) {
   p.ce_coef = d->bins ? (float)((double)d->ce_weight / (double)d->pixels_global) : 0.f;
   p.reg_weight = d->reg_weight;
   const dim3 grid(loss_blocks(d->pixels));
-  const int lpp = d->nb / 8;
-  const bool vec = d->dtype == ADN_BF16 && d->ld == d->nb && d->nb % 8 == 0 && (lpp & (lpp - 1)) == 0 &&
-                   (reinterpret_cast<uintptr_t>(d->logits) & 15) == 0 && (reinterpret_cast<uintptr_t>(d->dlogits) & 15) == 0;
-  if (vec) {
-    switch (lpp) {
-#define ADN_COARSE_VEC(L) case L: hipLaunchKernelGGL((coarse_loss_vec_kernel<L>), grid, dim3(256), 0, st, p); break;
-      ADN_COARSE_VEC(1) ADN_COARSE_VEC(2) ADN_COARSE_VEC(4) ADN_COARSE_VEC(8) ADN_COARSE_VEC(16) ADN_COARSE_VEC(32) ADN_COARSE_VEC(64)
-#undef ADN_COARSE_VEC
-    }
-  } else if (d->dtype == ADN_BF16) {
-    hipLaunchKernelGGL((coarse_loss_kernel<uint16_t>), grid, dim3(256), 0, st, p);
-  } else {
-    hipLaunchKernelGGL((coarse_loss_kernel<float>), grid, dim3(256), 0, st, p);
-  }
+  launch_bin_rows(d->dtype, d->nb, d->ld, d->logits, d->dlogits, [&](auto row) {
+    hipLaunchKernelGGL((coarse_loss_kernel<typename decltype(row)::type>), grid, dim3(256), 0, st, p);
+  });
   ADN_CHECK_LAUNCH();
   return ADN_OK;
 }

@@ -3,19 +3,14 @@
 // the 1x1 single-channel depth head, and the L1 + total-variation depth loss.
 // All activations NHWC in dtype T (f32 / bf16); 8 channels (16/32 bytes) per thread when C % 8 == 0,
 // scalar otherwise.  HBM roofline kernels: every tensor is read/written exactly once per pass.
-#include "adn_common.h"
+#include "loss_tail.h"
 #include "mx8_quant.h"
 #include "epilogue.h"
 
 namespace {
 
 constexpr int kMaxBlocks = 8192;
-inline unsigned blocks_for(int64_t n, int per_block = 256) {
-  int64_t b = adn_cdiv(n, per_block);
-  if (b > kMaxBlocks) b = kMaxBlocks;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
+inline unsigned blocks_for(int64_t n, int per_block = 256) { return adn_grid_blocks(n, per_block, kMaxBlocks); }
 
 template <typename T, int V>
 __device__ __forceinline__ void loadv(const T* p, int64_t idx, float* f) {
@@ -581,42 +576,26 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* partials, int6
 // unmasked.  stats (f64[4]) = [sum|p-g|, sum|dx|, sum|dy|, 0].
 __global__ __launch_bounds__(256) void l1tv_stats_kernel(const float* pred, const float* gt, int64_t n, int H, int W,
                                                          double* partial) {
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  double s[3] = {0.0, 0.0, 0.0};
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
     const int x = (int)(e % W);
     const int y = (int)((e / W) % H);
     const float p = pred[e];
-    s0 += (double)fabsf(p - gt[e]);
-    if (x < W - 1) s1 += (double)fabsf(p - pred[e + 1]);
-    if (y < H - 1) s2 += (double)fabsf(p - pred[e + W]);
+    s[0] += (double)fabsf(p - gt[e]);
+    if (x < W - 1) s[1] += (double)fabsf(p - pred[e + 1]);
+    if (y < H - 1) s[2] += (double)fabsf(p - pred[e + W]);
   }
-  __shared__ double sm[3][4];
-  s0 = wave_sum_d(s0);
-  s1 = wave_sum_d(s1);
-  s2 = wave_sum_d(s2);
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    sm[0][wv] = s0;
-    sm[1][wv] = s1;
-    sm[2][wv] = s2;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3)
-    partial[(int64_t)blockIdx.x * 3 + threadIdx.x] =
-        sm[threadIdx.x][0] + sm[threadIdx.x][1] + sm[threadIdx.x][2] + sm[threadIdx.x][3];
+  block_partial_row(s, partial + (int64_t)blockIdx.x * 3);
 }
 
 __global__ __launch_bounds__(64) void l1tv_stats_final_kernel(const double* partial, int nb, double* stats) {
-  for (int q = 0; q < 3; ++q) {
-    double s = 0.0;
-    for (int r = threadIdx.x; r < nb; r += 64) s += partial[(int64_t)r * 3 + q];
-    s = wave_sum_d(s);
-    if (threadIdx.x == 0) stats[q] = s;
+  double s[3];
+  sum_partial_rows_wave(partial, nb, s);
+  if (threadIdx.x == 0) {
+    for (int q = 0; q < 3; ++q) stats[q] = s[q];
+    stats[3] = 0.0;
   }
-  if (threadIdx.x == 0) stats[3] = 0.0;
 }
-
-__device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
 
 // counts: N = n * world, Nx = B*H*(W-1) * world, Ny = B*(H-1)*W * world (world = data-parallel replicas whose
 // stats were summed).  loss_out optional (block 0 writes it).
@@ -631,11 +610,11 @@ __global__ __launch_bounds__(256) void l1tv_finish_kernel(const float* pred, con
     const int x = (int)(e % W);
     const int y = (int)((e / W) % H);
     const float p = pred[e];
-    float g = c0 * sgn(p - gt[e]);
-    if (x < W - 1) g += cx * sgn(p - pred[e + 1]);
-    if (x > 0) g -= cx * sgn(pred[e - 1] - p);
-    if (y < H - 1) g += cy * sgn(p - pred[e + W]);
-    if (y > 0) g -= cy * sgn(pred[e - W] - p);
+    float g = c0 * adn_sgn(p - gt[e]);
+    if (x < W - 1) g += cx * adn_sgn(p - pred[e + 1]);
+    if (x > 0) g -= cx * adn_sgn(pred[e - 1] - p);
+    if (y < H - 1) g += cy * adn_sgn(p - pred[e + W]);
+    if (y > 0) g -= cy * adn_sgn(pred[e - W] - p);
     grad[e] = g;
   }
 }
@@ -943,10 +922,7 @@ extern "C" int adn_head1x1_bwd(const float* gout, const float* zpre, const void*
 
 extern "C" int64_t adn_l1tv_workspace_bytes(int64_t n) {
   if (n <= 0) return -1;
-  int64_t nb = adn_cdiv(n, 256 * 8);
-  if (nb > 1024) nb = 1024;
-  if (nb < 1) nb = 1;
-  return nb * 3 * (int64_t)sizeof(double);
+  return (int64_t)adn_grid_blocks(n, 256 * 8, 1024) * 3 * (int64_t)sizeof(double);
 }
 
 extern "C" int adn_l1tv_stats(const float* pred, const float* gt, int32_t B, int32_t H, int32_t W, double* stats,

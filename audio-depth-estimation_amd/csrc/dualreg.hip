@@ -4,11 +4,9 @@
 //   dualreg_loss     ONE pass over the pixels: final = coarse + offset, and with a target the three L1 sums
 //                    (masked |coarse - gt|, masked |final - gt|, |offset|) and the gradients of their weighted means
 //   dualreg_finish   per-block f64 partials -> sums -> (coarse, final, offset_reg, total)
-#include "adn_common.h"
+#include "loss_tail.h"
 
 namespace {
-
-constexpr int kMaxBlocks = 2048;
 
 struct DualRegP {
   const float* coarse; const float* offset; const float* gt; const double* n_valid;
@@ -18,10 +16,7 @@ struct DualRegP {
   float cw, fw, rw;
 };
 
-__device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }      // torch's abs backward
-
 __global__ __launch_bounds__(256) void dualreg_loss_kernel(DualRegP p) {
-  __shared__ double sm[3][4];
   const bool have_loss = p.gt != nullptr;
   // no valid pixel in the global batch: DualRegressionLoss takes the unmasked mean (its valid_mask.any() else-branch)
   bool all = false;
@@ -33,7 +28,7 @@ __global__ __launch_bounds__(256) void dualreg_loss_kernel(DualRegP p) {
     inv_pix = (float)(1.0 / p.pixels_global);
   }
   const float rcoef = p.rw * inv_pix;
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+  double a[3] = {0.0, 0.0, 0.0};
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < p.pixels; e += (int64_t)gridDim.x * 256) {
     const float c = p.coarse[e], o = p.offset[e];
     const float f = c + o;
@@ -42,71 +37,33 @@ __global__ __launch_bounds__(256) void dualreg_loss_kernel(DualRegP p) {
     const float g = p.gt[e];
     const float m = (all || g > 0.f) ? 1.f : 0.f;
     const float dc = c - g, df = f - g;
-    a0 += (double)(m * fabsf(dc));
-    a1 += (double)(m * fabsf(df));
-    a2 += (double)fabsf(o);
-    const float gf = p.fw * sgn(df) * m * inv_n;
-    p.dcoarse[e] = p.cw * sgn(dc) * m * inv_n + gf;
-    p.doffset[e] = gf + rcoef * sgn(o);
+    a[0] += (double)(m * fabsf(dc));
+    a[1] += (double)(m * fabsf(df));
+    a[2] += (double)fabsf(o);
+    const float gf = p.fw * adn_sgn(df) * m * inv_n;
+    p.dcoarse[e] = p.cw * adn_sgn(dc) * m * inv_n + gf;
+    p.doffset[e] = gf + rcoef * adn_sgn(o);
   }
-  if (!have_loss) return;
-  a0 = wave_sum_d(a0);
-  a1 = wave_sum_d(a1);
-  a2 = wave_sum_d(a2);
-  if ((threadIdx.x & 63) == 0) {
-    sm[0][threadIdx.x >> 6] = a0;
-    sm[1][threadIdx.x >> 6] = a1;
-    sm[2][threadIdx.x >> 6] = a2;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3)
-    p.partial[(int64_t)blockIdx.x * 3 + threadIdx.x] =
-        sm[threadIdx.x][0] + sm[threadIdx.x][1] + sm[threadIdx.x][2] + sm[threadIdx.x][3];
+  if (have_loss) block_partial_row(a, p.partial + (int64_t)blockIdx.x * 3);
 }
 
 // one block: partial [rows][3] -> sums[3] (skipped when partial is NULL: the sums were all-reduced by the caller), then
 // terms = (coarse, final, offset_reg, total)
 __global__ __launch_bounds__(256) void dualreg_finish_kernel(const double* partial, int rows, double* sums, const double* n_valid,
                                                              double pixels_global, float cw, float fw, float rw, float* terms) {
-  __shared__ double sm[3][4];
-  if (partial) {
-    double a[3] = {0.0, 0.0, 0.0};
-    for (int r = threadIdx.x; r < rows; r += 256)
-      for (int k = 0; k < 3; ++k) a[k] += partial[(int64_t)r * 3 + k];
-    for (int k = 0; k < 3; ++k) {
-      a[k] = wave_sum_d(a[k]);
-      if ((threadIdx.x & 63) == 0) sm[k][threadIdx.x >> 6] = a[k];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    double s[3];
-    for (int k = 0; k < 3; ++k) {
-      if (partial) {
-        s[k] = sm[k][0] + sm[k][1] + sm[k][2] + sm[k][3];
-        sums[k] = s[k];
-      } else {
-        s[k] = sums[k];
-      }
-    }
-    if (terms) {
-      const double nv = n_valid[0];
-      const double n = nv > 0.0 ? nv : pixels_global;
-      const float lc = (float)(s[0] / n), lf = (float)(s[1] / n), lo = (float)(s[2] / pixels_global);
-      terms[0] = lc;
-      terms[1] = lf;
-      terms[2] = lo;
-      terms[3] = cw * lc + fw * lf + rw * lo;
-    }
-  }
+  sum_partial_rows<3>(partial, rows, sums, [&](const double (&s)[3]) {
+    if (!terms) return;
+    const double nv = n_valid[0];
+    const double n = nv > 0.0 ? nv : pixels_global;
+    const float lc = (float)(s[0] / n), lf = (float)(s[1] / n), lo = (float)(s[2] / pixels_global);
+    terms[0] = lc;
+    terms[1] = lf;
+    terms[2] = lo;
+    terms[3] = cw * lc + fw * lf + rw * lo;
+  });
 }
 
-inline int loss_blocks(int64_t pixels) {
-  int64_t b = adn_cdiv(pixels, 256);
-  if (b > kMaxBlocks) b = kMaxBlocks;
-  if (b < 1) b = 1;
-  return (int)b;
-}
+inline int loss_blocks(int64_t pixels) { return adn_grid_blocks(pixels, 256, kLossBlocks); }
 
 }  // namespace
 

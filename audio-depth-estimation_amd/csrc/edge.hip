@@ -592,12 +592,8 @@ __global__ __launch_bounds__(256) void thin_wgrad_sum_kernel(const float* slab, 
   }
 }
 
-inline int edge_blocks(int64_t units, int cap) {       // 4 waves per workgroup, >= 2 units per wave when there is enough work
-  int64_t b = adn_cdiv(units, 8);
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
+// 4 waves per workgroup, >= 2 units per wave when there is enough work
+inline int edge_blocks(int64_t units, int cap) { return adn_grid_blocks(units, 8, cap); }
 constexpr int kPixBlocks = 2048;    // l0_fwd: 8 workgroups per CU
 constexpr int kDgradBlocks = 768;   // d0_dgrad: 3 workgroups per CU (143 VGPRs), ~11 pixel groups per wave at B = 32
 constexpr int kWgradBlocks = 512;   // thin_wgrad: 2 per CU (64 KiB of LDS each), >= 8 K-steps per wave at B = 32

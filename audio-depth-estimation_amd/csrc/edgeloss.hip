@@ -48,7 +48,6 @@ __device__ __forceinline__ float dilated_valid(const float* gt, int y, int x, in
     }
   return m;
 }
-__device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
 
 // partial sums per block: n valid, sum |pred - gt| valid, n dilated, sum |pg - gg| dilated, sum smooth
 __global__ __launch_bounds__(256) void edge_stats_kernel(const float* pred, const float* gt, int B, int H, int W,
@@ -119,10 +118,10 @@ __global__ __launch_bounds__(256) void edge_fields_kernel(const float* pred, con
     const float ve = dilated_valid(g, y, x, H, W);
     const Px sp = sobel(p, y, x, H, W), sg = sobel(g, y, x, H, W);
     const float pg = sqrtf(sp.sx * sp.sx + sp.sy * sp.sy + kEps), gg = sqrtf(sg.sx * sg.sx + sg.sy * sg.sy + kEps);
-    const float a = cE * ve * sgn(pg * ve - gg * ve);        // d / d pg of |pg ve - gg ve| / n_dilated
+    const float a = cE * ve * adn_sgn(pg * ve - gg * ve);        // d / d pg of |pg ve - gg ve| / n_dilated
     const float bsm = cS * expf(-gg) * v;
-    fx[e] = a * sp.sx / pg + bsm * sgn(sp.sx);
-    fy[e] = a * sp.sy / pg + bsm * sgn(sp.sy);
+    fx[e] = a * sp.sx / pg + bsm * adn_sgn(sp.sx);
+    fy[e] = a * sp.sy / pg + bsm * adn_sgn(sp.sy);
   }
 }
 
@@ -139,7 +138,7 @@ __global__ __launch_bounds__(256) void edge_grad_kernel(const float* pred, const
     const int64_t b = e / ((int64_t)W * H);
     const int64_t base = b * H * W;
     const float gv = gt[e];
-    float acc = gv > 0.f ? cR * sgn(pred[e] - gv) : 0.f;
+    float acc = gv > 0.f ? cR * adn_sgn(pred[e] - gv) : 0.f;
 #pragma unroll
     for (int dy = -1; dy <= 1; ++dy)
 #pragma unroll

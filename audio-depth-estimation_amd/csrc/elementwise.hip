@@ -7,22 +7,14 @@
 namespace {
 
 constexpr int kMaxBlocks = 4096;
-inline unsigned blocks_for(int64_t n, int per_block = 256) {
-  int64_t b = adn_cdiv(n, per_block);
-  if (b > kMaxBlocks) b = kMaxBlocks;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
+inline unsigned blocks_for(int64_t n, int per_block = 256) { return adn_grid_blocks(n, per_block, kMaxBlocks); }
 
 // BatchNorm apply kernels (bn_act / bn_bwd_apply): 1024 workgroups -- a thread keeps its 8 channels' coefficients in
 // registers over >= 4x more 16-byte chunks than at 4096 (bn_bwd_apply of the headline step 133 -> 115 us, of RGBDepthNet
 // 1.48 -> 1.02 ms together with the hoisted coefficient loads; 8192: 134 / 1.08, 2048: 122 / 1.02).  ADN_BN_BLOCKS overrides.
 inline unsigned bn_blocks_for(int64_t n) {
   static const int cap = getenv("ADN_BN_BLOCKS") ? atoi(getenv("ADN_BN_BLOCKS")) : 1024;
-  int64_t b = adn_cdiv(n, 256);
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (unsigned)b;
+  return adn_grid_blocks(n, 256, cap);
 }
 
 // master [X][4][4][Y] f32 -> s2 [X][16][Ypad] (cast, zero padded channels): coalesced both sides

@@ -298,12 +298,7 @@ __global__ __launch_bounds__(256) void optimizer_step_kernel(float* params, cons
   }
 }
 
-inline unsigned red_blocks(int64_t n) {
-  int64_t b = adn_cdiv(n, 256 * 8);
-  if (b > kRedBlocks) b = kRedBlocks;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
+inline unsigned red_blocks(int64_t n) { return adn_grid_blocks(n, 256 * 8, kRedBlocks); }
 
 }  // namespace
 

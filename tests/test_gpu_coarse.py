@@ -2,7 +2,9 @@
 
   * adn_coarse_targets against torch.bucketize / clamp / count: exact, including values that sit on an edge;
   * adn_coarse_loss against a float64 torch-CPU restatement with autograd (written here with log_softmax), on the same
-    inputs (bf16 logits: the bf16-rounded values upcast to f64).  Bars: depth and the three terms <= 2e-4 relative;
+    inputs (bf16 logits: the bf16-rounded values upcast to f64), on every kernel form (f32 / bf16, each vector width, wave
+    per pixel, padded rows) at 1, 63, 257 and ~2 048 pixels and, bf16, just past one pass of the 8- and 128-bin grids.
+    Bars: depth and the three terms <= 2e-4 relative;
     dlogits f32 <= 2e-4 of max|ref|; dlogits bf16 per element <= 2^-8 |ref| + 2e-4 max|ref| (one bf16 rounding of the output
     plus the f32 bar); padding columns exactly 0; two runs bit-identical; argmax == torch.argmax;
   * the model and the fused step against the golden vectors of the REFERENCE (tests/golden/coarse32_bc64.npz), f32 compute,
@@ -111,11 +113,15 @@ def _loss_case(mode, dtype, nb, ld, pixels, all_invalid=False):
     edges, centers = _bins_of(nb)
     g = torch.Generator().manual_seed(1000 * mode + nb + pixels)
     logits = (3.0 * torch.randn(pixels, ld, generator=g)).to(dtype)
-    logits[5, :nb] = 0.0                                                  # a tie: the first maximum wins
+    if pixels > 5:
+        logits[5, :nb] = 0.0                                              # a tie: the first maximum wins
     gt = 31.0 * torch.rand(pixels, generator=g)
     gt[torch.rand(pixels, generator=g) < 0.1] = 0.0                       # ~10 % invalid
     if all_invalid:
         gt.zero_()
+    elif not bool((gt > 0).any()):
+        gt[0] = 15.5                                                      # a single pixel that drew "invalid"
+    assert all_invalid or int((gt > 0).sum()) > 0                         # else the regression term is NaN by definition
     bins = torch.clamp(torch.bucketize(gt, edges[1:-1].contiguous()), 0, nb - 1)
     x64 = logits[:, :nb].double().requires_grad_(True)
     depth_r, ce_r, reg_r, tot_r = _restatement(x64, centers.double(), bins, gt.double(), mode, sigma, gamma, cew, regw)
@@ -155,19 +161,28 @@ def _loss_case(mode, dtype, nb, ld, pixels, all_invalid=False):
     if ld > nb:
         assert float(dl[:, nb:].abs().max()) == 0.0
     assert torch.equal(am.long(), torch.argmax(logits[:, :nb].float(), dim=1))
-    assert int(am[5]) == 0
+    assert pixels <= 5 or int(am[5]) == 0
     # forward only (no bins, no gradient): the same depth bits
     depth2 = torch.empty(pixels, device=DEV)
     K.coarse_loss(lg, nb, cen, depth2)
     assert torch.equal(depth2.cpu(), depth)
 
 
-@pytest.mark.parametrize('pixels', [2 * 33 * 31, 2 * 32 * 32])
-@pytest.mark.parametrize('nb,ld', [(8, 64), (100, 128), (128, 128), (256, 256)])
+# every width of the vector form (nb = ld = 8 .. 512), nb / 8 = 3 (no vector form), padded rows; 1, 63 and 257 pixels:
+# less than one wave-iteration, dead lanes in the last one, more than one block
+@pytest.mark.parametrize('pixels', [2 * 33 * 31, 2 * 32 * 32, 1, 63, 257])
+@pytest.mark.parametrize('nb,ld', [(8, 64), (100, 128), (128, 128), (256, 256), (8, 8), (16, 16), (32, 32), (64, 64),
+                                   (512, 512), (24, 24)])
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize('mode', [0, 1, 2])
 def test_coarse_loss_vs_float64(mode, dtype, nb, ld, pixels):
     _loss_case(mode, dtype, nb, ld, pixels)
+
+
+@pytest.mark.parametrize('nb,pixels', [(8, 2048 * 4 * 64 + 1), (128, 2048 * 4 * 4 + 1)])
+def test_coarse_loss_vs_float64_past_one_grid_pass(nb, pixels):
+    """One pixel more than the 2048-block grid of that vector width serves in one pass (64 / (nb / 8) pixels per wave)."""
+    _loss_case(0, torch.bfloat16, nb, nb, pixels)
 
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
