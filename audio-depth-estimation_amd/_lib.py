@@ -271,6 +271,10 @@ _PROTOS = {
     'adn_vae_fwd': (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, C.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_int32, c_void_p, c_void_p]),
+    'adn_vae_sample': (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, C.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    'adn_sample_stats': (C.c_int, [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]),
     'adn_vae_bwd_workspace_bytes': (c_int64, [c_int32, c_int32]),
     'adn_vae_bwd': (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

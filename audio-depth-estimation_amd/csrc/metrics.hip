@@ -130,7 +130,74 @@ __global__ __launch_bounds__(MT) void compute_errors_kernel(const float* gt_all,
   }
 }
 
+// Per-pixel mean and unbiased standard deviation over K samples (samples [K][N]): one read of the samples, the two
+// moments of the DEVIATIONS d = x - x[0] from the pixel's first sample in registers, mean = x[0] + sum(d) / K and
+// variance = (sum(d^2) - sum(d)^2 / K) / (K - 1).  The shift is one of the samples, so |mean(d)| <= sqrt(K) * std and the
+// subtraction cancels at most a factor ~K (K^2 * 2^-24 relative, worst case), whatever the depth: 25 m +- 1 cm keeps its
+// spread in f32, where the same formula on x itself (or Welford's running mean, rounded at 25 m every step) does not.
+// Streaming: (K + 2) * N * 4 bytes.  V = 4: N % 4 == 0, every row 16-byte aligned, one float4 column per thread;
+// V = 1: any N, scalar accesses.
+template <int V>
+__global__ __launch_bounds__(256) void sample_stats_kernel(const float* __restrict__ samples, int32_t K, int64_t N,
+                                                           float* __restrict__ mean, float* __restrict__ stdev) {
+  const int64_t cols = N / V, stride = (int64_t)gridDim.x * 256;
+  const float inv = K > 1 ? 1.0f / (float)(K - 1) : 0.f;
+  for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < cols; c += stride) {
+    const float* p = samples + c * V;
+    float x0[V], s1[V], s2[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) x0[v] = s1[v] = s2[v] = 0.f;
+#pragma unroll 4
+    for (int k = 0; k < K; ++k) {
+      float x[V];
+      if constexpr (V == 4) {
+        const float4 q = *reinterpret_cast<const float4*>(p + (int64_t)k * N);
+        x[0] = q.x, x[1] = q.y, x[2] = q.z, x[3] = q.w;
+      } else {
+        x[0] = p[(int64_t)k * N];
+      }
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        if (k == 0) x0[v] = x[v];
+        const float d = x[v] - x0[v];
+        s1[v] += d;
+        s2[v] = fmaf(d, d, s2[v]);
+      }
+    }
+    float m[V], s[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const float t = s1[v] / (float)K;
+      m[v] = x0[v] + t;
+      s[v] = sqrtf(fmaxf(fmaf(-s1[v], t, s2[v]), 0.f) * inv);
+    }
+    if constexpr (V == 4) {
+      *reinterpret_cast<float4*>(mean + c * 4) = make_float4(m[0], m[1], m[2], m[3]);
+      *reinterpret_cast<float4*>(stdev + c * 4) = make_float4(s[0], s[1], s[2], s[3]);
+    } else {
+      mean[c] = m[0];
+      stdev[c] = s[0];
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int adn_sample_stats(const float* samples, int32_t K, int64_t N, float* mean, float* stdev, void* stream) {
+  ADN_CHECK_ARG(K >= 1 && N >= 1, "adn_sample_stats: K %d, N %lld (need K >= 1, N >= 1)", K, (long long)N);
+  ADN_CHECK_ARG(samples && mean && stdev, "adn_sample_stats: null pointer");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const bool vec = N % 4 == 0 && ((reinterpret_cast<uintptr_t>(samples) | reinterpret_cast<uintptr_t>(mean) |
+                                   reinterpret_cast<uintptr_t>(stdev)) & 15) == 0;
+  if (vec)
+    hipLaunchKernelGGL(sample_stats_kernel<4>, dim3(adn_grid_blocks(N / 4, 256, 2048)), dim3(256), 0, st, samples, K, N,
+                       mean, stdev);
+  else
+    hipLaunchKernelGGL(sample_stats_kernel<1>, dim3(adn_grid_blocks(N, 256, 2048)), dim3(256), 0, st, samples, K, N, mean,
+                       stdev);
+  ADN_CHECK_LAUNCH();
+  return ADN_OK;
+}
 
 extern "C" int64_t adn_compute_errors_workspace_bytes(int32_t, int64_t) { return 0; }
 

@@ -23,19 +23,11 @@ __device__ __forceinline__ float vae_gauss(uint64_t seed, int64_t idx) {
   return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958648f * u2);
 }
 
-// mu / logvar / eps / z: one wave per (latent row j, group of kVB images); lanes stride over C.
-__global__ __launch_bounds__(256) void vae_encode_kernel(const float* __restrict__ h, int B, int C, int L,
-                                                         const float* __restrict__ w_mu, const float* __restrict__ b_mu,
-                                                         const float* __restrict__ w_lv, const float* __restrict__ b_lv,
-                                                         uint64_t seed, const double* counter,
-                                                         const float* __restrict__ eps_in, float* mu, float* logvar,
-                                                         float* eps, float* z) {
-  const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int nbg = (B + kVB - 1) / kVB;
-  if (wave >= L * nbg) return;                                  // wave-uniform
-  if (counter) seed += 0xD1B54A32D192ED03ull * (uint64_t)(counter[0] + 1.0);     // device step count: replay safe
-  const int j = wave % L, b0 = (wave / L) * kVB;
-  const int nb = min(kVB, B - b0);
+// Row j of fc_mu / fc_logvar against images b0 .. b0 + nb - 1 (one wave, lanes stride over C): lane k < nb ends up with
+// image b0 + k's two dot products (no bias yet).  Shared by the training forward and the multi-draw sampler.
+__device__ __forceinline__ void vae_mu_logvar_dots(const float* __restrict__ h, int C, const float* __restrict__ w_mu,
+                                                   const float* __restrict__ w_lv, int j, int b0, int nb, int lane,
+                                                   float& m, float& l) {
   float am[kVB], al[kVB];
 #pragma unroll
   for (int k = 0; k < kVB; ++k) am[k] = al[k] = 0.f;
@@ -52,7 +44,7 @@ __global__ __launch_bounds__(256) void vae_encode_kernel(const float* __restrict
       }
     }
   }
-  float m = 0.f, l = 0.f;
+  m = l = 0.f;
 #pragma unroll
   for (int k = 0; k < kVB; ++k) {
     const float sm = wave_sum(am[k]), sl = wave_sum(al[k]);
@@ -61,6 +53,23 @@ __global__ __launch_bounds__(256) void vae_encode_kernel(const float* __restrict
       l = sl;
     }
   }
+}
+
+// mu / logvar / eps / z: one wave per (latent row j, group of kVB images); lanes stride over C.
+__global__ __launch_bounds__(256) void vae_encode_kernel(const float* __restrict__ h, int B, int C, int L,
+                                                         const float* __restrict__ w_mu, const float* __restrict__ b_mu,
+                                                         const float* __restrict__ w_lv, const float* __restrict__ b_lv,
+                                                         uint64_t seed, const double* counter,
+                                                         const float* __restrict__ eps_in, float* mu, float* logvar,
+                                                         float* eps, float* z) {
+  const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int nbg = (B + kVB - 1) / kVB;
+  if (wave >= L * nbg) return;                                  // wave-uniform
+  if (counter) seed += 0xD1B54A32D192ED03ull * (uint64_t)(counter[0] + 1.0);     // device step count: replay safe
+  const int j = wave % L, b0 = (wave / L) * kVB;
+  const int nb = min(kVB, B - b0);
+  float m, l;
+  vae_mu_logvar_dots(h, C, w_mu, w_lv, j, b0, nb, lane, m, l);
   if (lane < nb) {
     const int64_t idx = (int64_t)(b0 + lane) * L + j;
     m += b_mu[j];
@@ -74,10 +83,45 @@ __global__ __launch_bounds__(256) void vae_encode_kernel(const float* __restrict
   }
 }
 
+// The sampler's form of the kernel above: mu / logvar once, then K draws z[k][b][j] = mu + eps[k][b][j] * exp(logvar / 2).
+// The drawn eps of draw k is element k * B * L + b * L + j of the stream of ``seed``: every (k, b, j) has a counter of
+// its own (no two draws share one), draw k does not depend on K, and draw 0 is what vae_encode_kernel draws for the seed.
+// draw == 0 (mean decode): eps = 0, z = mu.
+__global__ __launch_bounds__(256) void vae_sample_encode_kernel(const float* __restrict__ h, int B, int C, int L, int K,
+                                                                int draw, const float* __restrict__ w_mu,
+                                                                const float* __restrict__ b_mu,
+                                                                const float* __restrict__ w_lv,
+                                                                const float* __restrict__ b_lv, uint64_t seed,
+                                                                const float* __restrict__ eps_in, float* mu,
+                                                                float* logvar, float* eps, float* z) {
+  const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int nbg = (B + kVB - 1) / kVB;
+  if (wave >= L * nbg) return;                                  // wave-uniform
+  const int j = wave % L, b0 = (wave / L) * kVB;
+  const int nb = min(kVB, B - b0);
+  float m, l;
+  vae_mu_logvar_dots(h, C, w_mu, w_lv, j, b0, nb, lane, m, l);
+  if (lane < nb) {
+    const int64_t idx = (int64_t)(b0 + lane) * L + j, BL = (int64_t)B * L;
+    m += b_mu[j];
+    l += b_lv[j];
+    const float sd = expf(0.5f * l);
+    mu[idx] = m;
+    logvar[idx] = l;
+    for (int k = 0; k < K; ++k) {
+      const int64_t kidx = (int64_t)k * BL + idx;
+      const float e = !draw ? 0.f : (eps_in ? eps_in[kidx] : vae_gauss(seed, kidx));
+      eps[kidx] = e;
+      z[kidx] = m + e * sd;
+    }
+  }
+}
+
 // ReLU(fc_dec(z)) in the compute dtype: one wave per (output channel c, group of kVB images); lanes stride over L.
-// The last block computes the per-image KL and its batch mean (fixed order: wave w sums images w, w+4, ...).
+// The last block computes the per-image KL and its batch mean (fixed order: wave w sums images w, w+4, ...) over the
+// Bkl rows of mu / logvar: B in the training forward, B / K in the sampler, whose K draws share one mu / logvar.
 template <typename T>
-__global__ __launch_bounds__(256) void vae_decode_kernel(const float* __restrict__ z, int B, int C, int L,
+__global__ __launch_bounds__(256) void vae_decode_kernel(const float* __restrict__ z, int B, int Bkl, int C, int L,
                                                          const float* __restrict__ w_dec, const float* __restrict__ b_dec,
                                                          const float* __restrict__ mu, const float* __restrict__ logvar,
                                                          float* kl_img, float* kl, T* out) {
@@ -85,7 +129,7 @@ __global__ __launch_bounds__(256) void vae_decode_kernel(const float* __restrict
   if (blockIdx.x == gridDim.x - 1) {
     __shared__ float part[4];
     float acc = 0.f;
-    for (int b = wid; b < B; b += 4) {
+    for (int b = wid; b < Bkl; b += 4) {
       float s = 0.f;
       for (int j = lane; j < L; j += 64) {
         const float l = logvar[(int64_t)b * L + j], m = mu[(int64_t)b * L + j];
@@ -97,7 +141,7 @@ __global__ __launch_bounds__(256) void vae_decode_kernel(const float* __restrict
     }
     if (lane == 0) part[wid] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) kl[0] = (((part[0] + part[1]) + part[2]) + part[3]) / (float)B;
+    if (threadIdx.x == 0) kl[0] = (((part[0] + part[1]) + part[2]) + part[3]) / (float)Bkl;
     return;
   }
   const int wave = blockIdx.x * 4 + wid;
@@ -240,11 +284,41 @@ extern "C" int adn_vae_fwd(const float* h, int32_t B, int32_t C, int32_t L, cons
   ADN_CHECK_LAUNCH();
   const unsigned nb = (unsigned)adn_cdiv((int64_t)C * nbg, 4) + 1;
   if (dtype == ADN_BF16)
-    hipLaunchKernelGGL((vae_decode_kernel<uint16_t>), dim3(nb), dim3(256), 0, st, z, B, C, L, w_dec, b_dec, mu, logvar,
+    hipLaunchKernelGGL((vae_decode_kernel<uint16_t>), dim3(nb), dim3(256), 0, st, z, B, B, C, L, w_dec, b_dec, mu, logvar,
                        kl_img, kl, reinterpret_cast<uint16_t*>(out_relu));
   else
-    hipLaunchKernelGGL((vae_decode_kernel<float>), dim3(nb), dim3(256), 0, st, z, B, C, L, w_dec, b_dec, mu, logvar,
+    hipLaunchKernelGGL((vae_decode_kernel<float>), dim3(nb), dim3(256), 0, st, z, B, B, C, L, w_dec, b_dec, mu, logvar,
                        kl_img, kl, reinterpret_cast<float*>(out_relu));
+  ADN_CHECK_LAUNCH();
+  return ADN_OK;
+}
+
+extern "C" int adn_vae_sample(const float* h, int32_t B, int32_t C, int32_t L, int32_t K, int32_t mode,
+                              const float* w_mu, const float* b_mu, const float* w_lv, const float* b_lv,
+                              const float* w_dec, const float* b_dec, uint64_t seed, const float* eps_in, float* mu,
+                              float* logvar, float* eps, float* z, float* kl_img, float* kl, int32_t dtype,
+                              void* out_relu, void* stream) {
+  if (int rc = vae_check(B, C, L, dtype, "adn_vae_sample")) return rc;
+  ADN_CHECK_ARG(mode == ADN_VAE_DRAW || mode == ADN_VAE_MEAN, "adn_vae_sample: bad mode %d", mode);
+  ADN_CHECK_ARG(K >= 1 && (mode == ADN_VAE_DRAW || K == 1), "adn_vae_sample: K %d (need K >= 1, and K == 1 for the mean decode)",
+                K);
+  // the decode grid has one wave per (channel, group of kVB rows) of the K * B rows
+  const int64_t rows = (int64_t)K * B, nbg = adn_cdiv(rows, (int64_t)kVB);
+  ADN_CHECK_ARG(rows <= INT32_MAX && (int64_t)C * nbg <= INT32_MAX - 4,
+                "adn_vae_sample: K %d x B %d rows of %d channels exceed the decode grid", K, B, C);
+  ADN_CHECK_ARG(h && w_mu && b_mu && w_lv && b_lv && w_dec && b_dec && mu && logvar && eps && z && kl_img && kl && out_relu,
+                "adn_vae_sample: null pointer");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(vae_sample_encode_kernel, dim3((unsigned)adn_cdiv((int64_t)L * adn_cdiv(B, kVB), 4)), dim3(256), 0, st,
+                     h, B, C, L, K, mode == ADN_VAE_DRAW ? 1 : 0, w_mu, b_mu, w_lv, b_lv, seed, eps_in, mu, logvar, eps, z);
+  ADN_CHECK_LAUNCH();
+  const unsigned nb = (unsigned)adn_cdiv((int64_t)C * nbg, 4) + 1;
+  if (dtype == ADN_BF16)
+    hipLaunchKernelGGL((vae_decode_kernel<uint16_t>), dim3(nb), dim3(256), 0, st, z, (int)rows, B, C, L, w_dec, b_dec, mu,
+                       logvar, kl_img, kl, reinterpret_cast<uint16_t*>(out_relu));
+  else
+    hipLaunchKernelGGL((vae_decode_kernel<float>), dim3(nb), dim3(256), 0, st, z, (int)rows, B, C, L, w_dec, b_dec, mu,
+                       logvar, kl_img, kl, reinterpret_cast<float*>(out_relu));
   ADN_CHECK_LAUNCH();
   return ADN_OK;
 }

@@ -8,13 +8,18 @@ Replaces what PyTorch dispatches for /root/reference/models/unet_cvae_model.py (
   * head: identity (depth_norm) or ReLU, no Sigmoid.
 The three BatchNorms the reference builds but never calls (outermost downnorm / upnorm, innermost downnorm) are kept out of
 the flat buffers: no kernel, no gradient (their .grad stays None), no optimizer step, no optimizer state.
+Inference with K hypotheses per input (``CVAEEngine.sample``): the down path once, adn_vae_sample for K draws, the up path
+per draw with shared skips, adn_sample_stats for the per-pixel mean / std; on a buffer set of its own.
 """
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import torch
 
 from . import kernels as K
-from .engine import FusedTrainer, UNetEngine
+from ._lib import EPI_ACT, EPI_FINAL, EPI_RAW, GEMM_S2, GEMM_T2
+from .engine import BN_EPS, LEAKY, FusedTrainer, UNetEngine
 
 
 class CVAEEngine(UNetEngine):
@@ -31,6 +36,7 @@ class CVAEEngine(UNetEngine):
         # consuming a draw, so torch.manual_seed makes a run reproducible and the data order stays the reference's.
         self.vae_seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + 0x632BE59BD9B4E019) & 0xFFFFFFFFFFFFFFFF
         self.vae_draws = 0
+        self._sample_k = 0           # > 0 while sample() runs: _prepare builds / enters that (shape, K) sampling set
         self.step_counter = None
         self.eps_in = None           # f32 [B, L] device tensor: replaces the draw (tests inject the reference's eps)
         self.g_kl = None             # device f32 [1]: d loss / d kl for the backward
@@ -57,6 +63,8 @@ class CVAEEngine(UNetEngine):
         self.vae_kl_img = torch.empty(B, **f32)
         self.vae_kl = torch.zeros(1, **f32)
         self.vae_ws = torch.empty(max(K.vae_bwd_workspace_bytes(B, L), 16) // 4, **f32)
+        if self._sample_k:
+            self._prepare_sample(B, self._sample_k, dev)
 
     def _vae_params(self):
         v = self.vae
@@ -83,6 +91,138 @@ class CVAEEngine(UNetEngine):
         gd = self.levels[-1]['Gd']
         K.vae_bwd(gd, self.vae_h, self.vae_mu, self.vae_logvar, self.vae_eps, self.vae_z, wm, wl, wd, self.g_kl, *g, gd,
                   self.vae_ws, kl=self.vae_kl, loss=self.loss_acc)
+
+    # ------------------------------------------------------------------ multi-hypothesis inference
+    def _buffer_key(self, x):
+        key = super()._buffer_key(x)
+        return key + ('sample', self._sample_k) if self._sample_k else key
+
+    def _prepare_sample(self, B, Kn, dev):
+        """What a (B, K) sampling set holds beyond an ordinary set: the K draws and the K * B rows of the innermost
+        ``rd`` operand.  The up path then runs sample by sample on the set's own batch-B buffers."""
+        C, L = self.levels[-1]['cd_out'], self.vae.latent_dim
+        self.s_eps = torch.empty(Kn, B, L, dtype=torch.float32, device=dev)
+        self.s_z = torch.empty(Kn, B, L, dtype=torch.float32, device=dev)
+        self.s_rd = torch.empty(Kn * B, 1, 1, C, dtype=self.dtype, device=dev)
+
+    def sample(self, x, n_samples, mode='sample', eps=None, seed=None):
+        """K depth hypotheses for one input: the down path once, K draws from the bottleneck in one adn_vae_sample
+        call, the up path once per draw with the encoder's skips shared, mean / std by adn_sample_stats.
+
+        Eval mode only (BatchNorm from running statistics; nothing is written back).  ``mode='mean'`` decodes z = mu
+        (K = 1).  Noise: ``eps`` [K, B, L] is used as given; ``seed`` keys a reproducible draw; otherwise the draw
+        continues the engine's host counter (``vae_draws`` advances by K).  Runs on a buffer set of its own per
+        (input shape, K): the activations, tape and captured steps of a trainer on this engine are left alone."""
+        if self.module.training:
+            raise RuntimeError('UnetGeneratorVAE.sample runs in eval mode only (BatchNorm from running statistics): '
+                               'call model.eval() first')
+        if mode not in ('sample', 'mean'):
+            raise ValueError(f"sample mode must be 'sample' or 'mean', got {mode!r}")
+        if not x.is_cuda:
+            raise RuntimeError('UnetGeneratorVAE.sample needs a HIP device tensor (libadn has no CPU path)')
+        Kn = 1 if mode == 'mean' else int(n_samples)
+        if Kn < 1:
+            raise ValueError(f'n_samples must be >= 1, got {n_samples}')
+        if eps is not None and mode == 'sample':
+            want = (Kn, x.shape[0], self.vae.latent_dim)
+            if tuple(eps.shape) != want:
+                raise RuntimeError(f'eps has shape {tuple(eps.shape)}, {Kn} draws of this bottleneck are {want}')
+            eps = eps.to(device=x.device, dtype=torch.float32).contiguous()
+        else:
+            eps = None
+        x = x.contiguous().float()
+        if not self._bound():
+            self.bind_parameters()
+        prev_key = self._shape_key
+        flags = (self.weights_dirty, self.s2_fresh, self._packed_version)
+        self._sample_k = Kn
+        try:
+            with torch.no_grad():
+                return self._sample(x, Kn, mode, eps, seed)
+        finally:
+            self._sample_k = 0
+            # back to the set the caller was on (a trainer reads its KL and replays its captured step there), with its
+            # packed operands as valid as they were: sampling packed its own and changed no parameter
+            if prev_key is not None and prev_key != self._shape_key and self._shape_enter(prev_key):
+                self.weights_dirty, self.s2_fresh, self._packed_version = flags
+
+    def _sample(self, x, Kn, mode, eps, seed):
+        self._prepare(x)
+        T, B, n, L, ws = self.dtype, self.B, self.n, self.levels, self.workspace
+        if seed is not None:
+            call_seed = (int(seed) * 0x9E3779B97F4A7C15 + 0x632BE59BD9B4E019) & 0xFFFFFFFFFFFFFFFF
+        else:
+            call_seed = self.vae_seed ^ (((self.vae_draws + 1) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF)
+            if eps is None and mode == 'sample':
+                self.vae_draws += Kn
+        if self.weights_dirty or self._packed_version != self._version_sum():
+            self._pack_weights()
+        if not self.edge_path:
+            K.nchw_to_nhwc(x, self.x_nhwc)
+        # ---- down path, once, BatchNorm in eval form
+        for i, lv in enumerate(L):
+            src = self.x_nhwc if i == 0 else L[i - 1]['ad']
+            C, hs, wsz = lv['cd_out'], lv['hs'], lv['ws']
+            bn = lv['bn_d']
+            seg = dict(out0=lv['ad'], out1=lv['rd'], slope=LEAKY)
+            if self._vae_level(i):
+                K.igemm(T, GEMM_S2, B, hs, wsz, src, None, lv['down_s2'], C, EPI_RAW, [K.Seg(C, out0=self.vae_h)], ws)
+            elif i == 0 and self.edge_path:
+                K.l0_forward(x, self._flat_slice(self.flat_p, lv['down'].weight), B, hs, wsz, LEAKY, lv['ad'], lv['rd'])
+            elif bn is None:
+                K.igemm(T, GEMM_S2, B, hs, wsz, src, None, lv['down_s2'], C, EPI_ACT, [K.Seg(C, **seg)], ws,
+                        algo_c=lv['cd_in'])
+            else:
+                K.bn_eval_affine(bn.weight, bn.bias, bn.running_mean, bn.running_var, BN_EPS, lv['scale_d'],
+                                 lv['shift_d'])
+                K.igemm(T, GEMM_S2, B, hs, wsz, src, None, lv['down_s2'], C, EPI_ACT,
+                        [K.Seg(C, scale=lv['scale_d'], shift=lv['shift_d'], **seg)], ws)
+        # ---- bottleneck: mu / logvar once, K draws, the innermost rd operand for all K * B rows
+        fp = [self._flat_slice(self.flat_p, p) for p in self._vae_params()]
+        K.vae_sample(self.vae_h, *fp, call_seed, eps, self.vae_mu, self.vae_logvar, self.s_eps, self.s_z, self.vae_kl_img,
+                     self.vae_kl, self.s_rd, mode=K.VAE_MEAN if mode == 'mean' else K.VAE_DRAW)
+        # ---- up path: per draw, at batch B (the launches of forward(): same plans, same workspace), skips shared
+        for lv in L[1:]:
+            bn = lv['bn_u']
+            K.bn_eval_affine(bn.weight, bn.bias, bn.running_mean, bn.running_var, BN_EPS, lv['scale_u'], lv['shift_u'])
+        l0 = L[0]
+        out = torch.empty(Kn * B, 2 * l0['hs'], 2 * l0['ws'], l0['cu_out'], dtype=torch.float32, device=x.device)
+        for k in range(Kn):
+            rows = slice(k * B, (k + 1) * B)
+            for i in reversed(range(n)):
+                lv = L[i]
+                in0, in1 = (self.s_rd[rows], None) if i == n - 1 else self._up_inputs(i)
+                C, hs, wsz = lv['cu_out'], lv['hs'], lv['ws']
+                if i > 0:
+                    K.igemm(T, GEMM_T2, B, hs, wsz, in0, in1, lv['up_t2'], C, EPI_ACT,
+                            [K.Seg(C, out1=lv['ru'], scale=lv['scale_u'], shift=lv['shift_u'])], ws)
+                elif self.n1_path:
+                    K.convt_n1_forward(T, B, hs, wsz, in0, in1, self._flat_slice(self.flat_p, lv['up'].weight),
+                                       lv['up'].bias, self.final_act, out[rows], ws, relu_in0=self._skip_relu(i))
+                else:
+                    K.igemm(T, GEMM_T2, B, hs, wsz, in0, in1, lv['up_t2'], C, EPI_FINAL,
+                            [K.Seg(C, out0=out[rows], bias=lv['up'].bias, final_act=self.final_act)], ws)
+        H, W, Cout = out.shape[1], out.shape[2], out.shape[3]
+        if Cout == 1:
+            samples = out.view(Kn, B, 1, H, W)
+        else:
+            samples = torch.empty(Kn, B, Cout, H, W, dtype=torch.float32, device=out.device)
+            K.nhwc_to_nchw(out, samples.view(Kn * B, Cout, H, W))
+        mean, std = torch.empty_like(samples[0]), torch.empty_like(samples[0])
+        K.sample_stats(samples, mean, std)
+        return SampleResult(samples, mean, std, self.vae_mu.clone(), self.vae_logvar.clone(), self.vae_kl[0].clone(),
+                            self.s_eps.clone())
+
+
+class SampleResult(NamedTuple):
+    """What ``sample`` returns: f32 device tensors the caller owns."""
+    samples: torch.Tensor        # [K, B, C, H, W] depth hypotheses
+    mean: torch.Tensor           # [B, C, H, W] per-pixel mean over the K hypotheses
+    std: torch.Tensor            # [B, C, H, W] per-pixel unbiased std (0 for K = 1)
+    mu: torch.Tensor             # [B, L]
+    logvar: torch.Tensor         # [B, L]
+    kl: torch.Tensor             # 0-dim, the batch-mean KL
+    eps: torch.Tensor            # [K, B, L] the noise that was used (zeros for mode='mean')
 
 
 class _CVAEFunction(torch.autograd.Function):

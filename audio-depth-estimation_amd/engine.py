@@ -87,7 +87,7 @@ class UNetEngine(FlatParamEngine):
         if H % (1 << n) or W % (1 << n):
             raise RuntimeError(f'input {H}x{W} is not divisible by 2^{n}: Kernel size can\'t be greater than '
                                f'actual input size')
-        key = (B, Cin, H, W, x.device)
+        key = self._buffer_key(x)
         if self._shape_enter(key):
             return
         dev, T = x.device, self.dtype
@@ -247,6 +247,10 @@ class UNetEngine(FlatParamEngine):
         self.B = B
 
     # ------------------------------------------------------------------ topology hooks (cVAE: CVAEEngine)
+    def _buffer_key(self, x):
+        """Key of the per-shape buffer set an input runs on (CVAEEngine.sample: a set of its own per (shape, K))."""
+        return (*x.shape, x.device)
+
     def _vae_level(self, i):
         """Level whose down conv feeds the VAE bottleneck (raw f32 output, no activation)."""
         return self.vae is not None and i == self.n - 1

@@ -930,6 +930,42 @@ def vae_fwd(h, w_mu, b_mu, w_lv, b_lv, w_dec, b_dec, seed, counter, eps_in, mu, 
               ptr(kl), dtype_code(out_relu.dtype), ptr(out_relu), _stream())
 
 
+VAE_DRAW, VAE_MEAN = 0, 1                   # adn.h: mode of adn_vae_sample
+
+
+def vae_sample(h, w_mu, b_mu, w_lv, b_lv, w_dec, b_dec, seed, eps_in, mu, logvar, eps, z, kl_img, kl, out_relu,
+               mode=VAE_DRAW):
+    """K draws from one bottleneck (adn_vae_sample): mu / logvar [B, L] once; eps, z f32 [K, B, L]; out_relu [K * B, C]
+    (compute dtype) = ReLU(fc_dec(z)), row k * B + b.  eps_in (f32 [K, B, L]) replaces the draw; mode VAE_MEAN decodes
+    z = mu (K = 1)."""
+    B, Cc = h.shape[0], h.numel() // h.shape[0]
+    L = mu.shape[-1]
+    Kn = z.shape[0]
+    if z.dim() != 3 or Kn < 1:
+        raise RuntimeError(f'vae_sample: z must be [K, B, L] with K >= 1, got {tuple(z.shape)}')
+    _vae_shapes('vae_sample', B, Cc, L, h=(h, B * Cc), w_mu=(w_mu, L * Cc), b_mu=(b_mu, L), w_lv=(w_lv, L * Cc),
+                b_lv=(b_lv, L), w_dec=(w_dec, Cc * L), b_dec=(b_dec, Cc), eps_in=(eps_in, Kn * B * L), mu=(mu, B * L),
+                logvar=(logvar, B * L), eps=(eps, Kn * B * L), z=(z, Kn * B * L), kl_img=(kl_img, B), kl=(kl, 1),
+                out_relu=(out_relu, Kn * B * Cc))
+    _dev(h, w_mu, b_mu, w_lv, b_lv, w_dec, b_dec, eps_in, mu, logvar, eps, z, kl_img, kl, out_relu)
+    _lib.call('adn_vae_sample', ptr(h), B, Cc, L, Kn, mode, ptr(w_mu), ptr(b_mu), ptr(w_lv), ptr(b_lv), ptr(w_dec),
+              ptr(b_dec), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(eps_in), ptr(mu), ptr(logvar), ptr(eps), ptr(z), ptr(kl_img),
+              ptr(kl), dtype_code(out_relu.dtype), ptr(out_relu), _stream())
+
+
+def sample_stats(samples, mean, std):
+    """Per-element mean and unbiased std over dim 0 of ``samples`` (f32 [K, ...], contiguous) -> mean, std (f32, the
+    trailing shape): adn_sample_stats.  std is 0 for K = 1."""
+    Kn = samples.shape[0]
+    N = samples.numel() // max(Kn, 1)
+    for name, t, numel in (('samples', samples, Kn * N), ('mean', mean, N), ('std', std, N)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel:
+            raise RuntimeError(f'sample_stats: {name} must be contiguous float32 with {numel} elements, got '
+                               f'{tuple(t.shape)} {t.dtype}')
+    _dev(samples, mean, std)
+    _lib.call('adn_sample_stats', ptr(samples), Kn, N, ptr(mean), ptr(std), _stream())
+
+
 def vae_bwd_workspace_bytes(B, L):
     return _lib.load().adn_vae_bwd_workspace_bytes(B, L)
 

@@ -137,6 +137,20 @@ class UnetGeneratorVAE(nn.Module):
                                f'VAE bottleneck reads a 1x1 innermost map (got {tuple(input.shape)})')
         return run_cvae(self.engine(), input, self.training)
 
+    def sample(self, input, n_samples=8, mode='sample', eps=None, seed=None):
+        """``n_samples`` depth hypotheses for one input in one call (eval mode): the encoder runs once, the decoder once
+        per draw.  Returns a cvae_engine.SampleResult: samples [K, B, 1, H, W], their per-pixel mean / std
+        [B, 1, H, W], mu / logvar [B, L], kl.  ``mode='mean'`` decodes z = mu (K = 1, std = 0); ``eps`` [K, B, L]
+        replaces the draw; ``seed`` makes the draw reproducible, without it successive calls differ."""
+        if not isinstance(input, torch.Tensor) or not input.is_cuda:
+            raise RuntimeError('UnetGeneratorVAE.sample needs a HIP device tensor (libadn has no CPU path)')
+        side = 1 << self._num_downs
+        if input.dim() != 4 or input.shape[2] != side or input.shape[3] != side:
+            raise RuntimeError(f'UnetGeneratorVAE with {self._num_downs} downsamplings needs a {side}x{side} input: the '
+                               f'VAE bottleneck reads a 1x1 innermost map (got {tuple(input.shape)})')
+        with torch.no_grad():
+            return self.engine().sample(input, n_samples, mode=mode, eps=eps, seed=seed)
+
 
 def define_G_cvae(cfg, input_nc, output_nc, ngf, netG, norm='batch', use_dropout=False, init_type='normal',
                   init_gain=0.02, gpu_ids=None, latent_dim: int = 128):

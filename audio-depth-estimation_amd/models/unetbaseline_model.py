@@ -89,6 +89,10 @@ class DataParallel(nn.Module):
     def forward(self, *args, **kwargs):
         return self.module(*args, **kwargs)
 
+    def sample(self, *args, **kwargs):
+        """Multi-hypothesis inference of a wrapped cVAE generator (UnetGeneratorVAE.sample)."""
+        return self.module.sample(*args, **kwargs)
+
 
 def init_net(net, init_type='normal', init_gain=0.02, gpu_ids=[]):
     """Device placement, (key-compatible) DataParallel wrap and weight init (reference :42-57)."""

@@ -661,6 +661,24 @@ int adn_vae_bwd(const void* g_rec, int32_t dtype, int32_t B, int32_t C, int32_t 
                 const float* w_dec, const float* g_kl, float* dw_mu, float* db_mu, float* dw_lv, float* db_lv,
                 float* dw_dec, float* db_dec, const float* kl, float* loss, void* dh, void* workspace,
                 int64_t workspace_bytes, void* stream);
+/* Multi-hypothesis inference: mu, logvar [B][L] computed ONCE from h [B][C], then K draws
+ * z[k][b][:] = mu[b] + eps[k][b][:] * exp(logvar[b] / 2) and out_relu [K*B][C] (dtype) = ReLU(Linear(L,C)(z)), row
+ * k * B + b (sample-major).  eps, z: f32 [K][B][L], written; eps is copied from eps_in [K][B][L] when non-NULL, else
+ * drawn as element (k * B + b) * L + j of the counter-based stream of ``seed`` (the generator of the forward above): no two
+ * draws share a counter, draw k does not depend on K, draw 0 is the forward's draw for the same seed.
+ * mode ADN_VAE_MEAN: the deterministic decode z = mu (eps = 0; needs K == 1, eps_in ignored).  kl_img [B] and kl [1] as
+ * in the forward (they depend on mu / logvar only).  Two launches, no atomics, bit-reproducible.
+ * Needs the forward's shapes, K >= 1 and K * B rows within the decode grid (ADN_ERR_ARG otherwise). */
+enum { ADN_VAE_DRAW = 0, ADN_VAE_MEAN = 1 };
+int adn_vae_sample(const float* h, int32_t B, int32_t C, int32_t L, int32_t K, int32_t mode, const float* w_mu,
+                   const float* b_mu, const float* w_lv, const float* b_lv, const float* w_dec, const float* b_dec,
+                   uint64_t seed, const float* eps_in, float* mu, float* logvar, float* eps, float* z, float* kl_img,
+                   float* kl, int32_t dtype, void* out_relu, void* stream);
+/* Per-element mean and unbiased standard deviation (divide by K - 1; 0 for K == 1) over K samples: samples f32 [K][N]
+ * -> mean, stdev f32 [N].  One read of the samples; the variance is accumulated from the deviations from each element's
+ * first sample, so a centimetre spread around 25 m survives f32.  16-byte accesses when N % 4 == 0 and the three pointers are 16-byte
+ * aligned (every row then is), 4-byte accesses otherwise.  Any K >= 1, N >= 1. */
+int adn_sample_stats(const float* samples, int32_t K, int64_t N, float* mean, float* stdev, void* stream);
 
 /* Coarse-depth classification family (models/coarse_depth_model.py, train_coarse_depth.py:446-463): the loss head behind
  * the 1x1 class conv.  f32 arithmetic, f64 final reductions, no atomics, bit-reproducible.
