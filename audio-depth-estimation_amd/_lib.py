@@ -221,6 +221,13 @@ _PROTOS = {
     'adn_bn_bwd_finalize': (C.c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     'adn_bn_bwd_apply': (C.c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p]),
+    'adn_dropout_apply': (C.c_int, [c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p]),
+    'adn_inorm_workspace_bytes': (c_int64, [c_int32, c_int32, c_int32]),
+    'adn_inorm_form': (C.c_int, [c_int32, c_int32, c_int32]),
+    'adn_inorm_fwd': (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p]),
+    'adn_inorm_bwd': (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float,
+                                c_void_p, c_int64, c_void_p]),
     'adn_loss_stats': (C.c_int, [c_void_p, c_void_p, c_int64, c_float, c_int32, c_float, c_void_p, c_void_p,
                                  c_int64, c_void_p]),
     'adn_loss_workspace_bytes': (c_int64, [c_int64]),

@@ -6,7 +6,7 @@ This is the MI355X-side replacement of what PyTorch dispatches for the reference
 
 Data layout in HBM
   * activations: NHWC, dtype f32 (exact path) or bf16 (throughput path); per down level i the raw conv
-    output ``zd[i]`` (BN levels only) plus the two materialised consumer views ``ad[i]`` =
+    output ``zd[i]`` (BatchNorm / InstanceNorm levels only) plus the two materialised consumer views ``ad[i]`` =
     LeakyReLU(BN(z)) (operand of the next down conv) and ``rd[i]`` = ReLU(BN(z)) (skip operand of the
     same level's transposed conv); per up level ``zu[i]`` and ``ru[i]`` = ReLU(BN(zu)).  The skip
     concat (unetbaseline_model.py:235) is virtual: the consumer GEMM reads two base pointers.
@@ -46,8 +46,42 @@ class UNetEngine(FlatParamEngine):
         self.model_name = 'UnetGenerator'
         self.final_act = 1 if self.depth_norm else 0      # head: 0 ReLU, 1 Sigmoid, 2 identity (cVAE)
         self.vae = None                                    # cVAE bottleneck (CVAEEngine); None: the plain U-Net
+        for lv in self.levels:                             # (the cVAE's level dicts carry the BatchNorm keys only)
+            for k, v in (('in_d', False), ('in_u', False), ('drop', False), ('eps_d', None), ('eps_u', None)):
+                lv.setdefault(k, v)
+        self.uses_dropout = any(lv['drop'] for lv in self.levels)
+        # norm='batch' without dropout: the configuration the thin edge kernels and the data-parallel reducer are wired for
+        self.batch_only = all(lv['bn_u'] is not None for lv in self.levels[1:]) and not self.uses_dropout
+        # dropout masks: keyed by (seed, level, device step counter) under a fused trainer (a hipGraph replay draws fresh
+        # ones); by (seed, level, host draw count) otherwise.  The seed is the default CPU generator's, read without
+        # consuming a draw.
+        self.dropout_seed = torch.initial_seed()
+        self.step_counter = None
+        self.drop_draws = 0
+        self._drop_active = False
         self._init_flat()
         self._saved = None
+
+    DROP_P = 0.5                                           # nn.Dropout(0.5), unetbaseline_model.py:227
+
+    def set_dropout_seed(self, seed):
+        """Restart the dropout mask stream from ``seed`` (default: torch.initial_seed() at construction)."""
+        self.dropout_seed = int(seed)
+        self.drop_draws = 0
+
+    def dropout_masks(self):
+        """Keep masks of the last training forward as bool [B, C, H, W] tensors, outermost dropout level first."""
+        return [lv['keep_u'].permute(0, 3, 1, 2).bool() for lv in self.levels if lv['drop'] and lv.get('keep_u') is not None]
+
+    def _draw_masks(self):
+        """One fresh keep mask per dropout level (adn_dropout_mask; Bernoulli(1 - p) per element)."""
+        for i, lv in enumerate(self.levels):
+            if lv['drop']:
+                seed = self.dropout_seed * 1000003 + i * 7919
+                if self.step_counter is None:
+                    seed += self.drop_draws * 0x9E3779B97F4A7C15
+                K.dropout_mask(lv['keep_u'], self.DROP_P, seed, self.step_counter)
+        self.drop_draws += 1
 
     def _pack_weights(self):
         """Cast/pack the f32 master weights into the GEMM operand forms.
@@ -84,6 +118,12 @@ class UNetEngine(FlatParamEngine):
             self.bind_parameters()
         B, Cin, H, W = x.shape
         n = self.n
+        # (torch raises this from the first InstanceNorm2d that sees a 1 x 1 image, before the conv below it fails)
+        for i, lv in enumerate(self.levels):
+            if lv['in_d'] and (H >> (i + 1)) * (W >> (i + 1)) < 2:
+                raise ValueError(f'Expected more than 1 spatial element when training, got input size '
+                                 f'[{B}, {lv["down"].weight.shape[0]}, {H >> (i + 1)}, {W >> (i + 1)}] (InstanceNorm2d of '
+                                 f'level {i}: a {H}x{W} input is too small for {n} downsamplings)')
         if H % (1 << n) or W % (1 << n):
             raise RuntimeError(f'input {H}x{W} is not divisible by 2^{n}: Kernel size can\'t be greater than '
                                f'actual input size')
@@ -109,6 +149,7 @@ class UNetEngine(FlatParamEngine):
         # They read the thin operand (network input, output gradient) as planar f32: no channel padding at all.
         self.edge_path = (T == torch.bfloat16 and self.n1_path and n >= 2 and Cin == 2
                           and l0['down'].weight.shape[0] == 64 and cu_in0 == 128 and l0['bn_d'] is None
+                          and self.batch_only and l0['down'].bias is None
                           and (W // 2) % 32 == 0 and not os.environ.get('ADN_NO_EDGE'))
         if self.edge_path:
             self.cin_pad, self.cout_pad = Cin, cout0
@@ -136,11 +177,12 @@ class UNetEngine(FlatParamEngine):
             # the skip operand as its readers get it (level 0 with skip0_leaky: before the ReLU, see _skip_relu)
             lv['skip'] = lv['ad'] if i == 0 and self.skip0_leaky else lv['rd']
             lv['Gd'] = act(cd_out)
-            lv['zd'] = act(cd_out) if lv['bn_d'] is not None else None
+            lv['zd'] = act(cd_out) if lv['bn_d'] is not None or lv['in_d'] else None
             big = lambda c, h=hs, w_=wsz: torch.empty(B, 2 * h, 2 * w_, c, dtype=T, device=dev)
             if i > 0:
-                lv['zu'] = big(cu_out)
+                lv['zu'] = big(cu_out) if lv['bn_u'] is not None or lv['in_u'] else None
                 lv['ru'] = big(cu_out)
+                lv['keep_u'] = torch.ones(B, 2 * hs, 2 * wsz, cu_out, dtype=torch.uint8, device=dev) if lv['drop'] else None
                 lv['Gu'] = big(cu_out)
             else:
                 lv['out'] = torch.empty(B, 2 * hs, 2 * wsz, cu_out, **f32)
@@ -163,7 +205,7 @@ class UNetEngine(FlatParamEngine):
                 pu, w2 = 0, K.convt_n1_workspace_bytes(B, hs, wsz)                                  # D0 fwd
             else:
                 pu, w2 = K.igemm_query(T, GEMM_T2, B, hs, wsz, c_up0, c_up1, cu_out, [cu_out],     # Di fwd
-                                        epi=EPI_Z_STATS if lv['bn_u'] is not None else EPI_FINAL)
+                                        epi=EPI_Z_STATS if lv['bn_u'] is not None else (EPI_FINAL if i == 0 else EPI_ACT))
             pgu, w3 = (0, 0) if edge0 else K.igemm_query(T, GEMM_S2, B, hs, wsz, cu_out_p, 0, cu_in,   # Di dgrad
                                                          [c_up0, c_up1] if c_up1 else [c_up0], epi=EPI_BWD)
             pgd, w4 = (0, 0) if i == 0 else K.igemm_query(T, GEMM_T2, B, hs, wsz, cd_out, 0, cd_in, [cd_in], epi=EPI_BWD)  # Li dgrad
@@ -177,6 +219,14 @@ class UNetEngine(FlatParamEngine):
                 w5 = K.thin_wgrad_workspace_bytes(B, hs, wsz, 2, 64, 0)
                 w6 = K.thin_wgrad_workspace_bytes(B, hs, wsz, 1, 64, 64)
             ws_bytes = max(ws_bytes, w1, w2, w3, w4, w5, w6)
+            # instance-norm statistics and the bias gradients (channel sums of dz) share the workspace
+            for tag, C, px in (('d', cd_out, hs * wsz), ('u', cu_out, 4 * hs * wsz)):
+                if lv['in_' + tag]:
+                    ws_bytes = max(ws_bytes, K.inorm_workspace_bytes(B, px, C))
+                    lv[f'mean_{tag}'] = torch.empty(B * C, **f32)
+                    lv[f'istd_{tag}'] = torch.empty(B * C, **f32)
+                if lv['down' if tag == 'd' else 'up'].bias is not None and not (tag == 'u' and i == 0):
+                    ws_bytes = max(ws_bytes, K.channel_sum_workspace_bytes(B * px, C))
             lv.update(P_d=pd, P_u=pu, P_gu=pgu, P_gd=pgd)
             # small-image levels: their weight gradients ride in one multi-problem launch (adn_wgrad_multi)
             # patch-staged levels: candidates for the shared-split launch (see _patch_groups below)
@@ -328,6 +378,9 @@ class UNetEngine(FlatParamEngine):
             self._x_in, self._x_ver = x, x._version          # the first conv and its weight gradient read x itself
         else:
             K.nchw_to_nhwc(x, self.x_nhwc)
+        self._drop_active = bool(training) and self.uses_dropout
+        if self._drop_active:
+            self._draw_masks()
         # ---- down path
         for i, lv in enumerate(L):
             src = self.x_nhwc if i == 0 else L[i - 1]['ad']
@@ -338,9 +391,14 @@ class UNetEngine(FlatParamEngine):
                 self._vae_forward(training)
             elif i == 0 and self.edge_path:
                 K.l0_forward(x, self._flat_slice(self.flat_p, lv['down'].weight), B, hs, wsz, LEAKY, lv['ad'], lv['rd'])
+            elif lv['in_d']:              # raw z (+ bias) through the identity form of the ACT epilogue, then the norm
+                K.igemm(T, GEMM_S2, B, hs, wsz, src, None, lv['down_s2'], C, EPI_ACT,
+                        [K.Seg(C, out0=lv['zd'], bias=lv['down'].bias, slope=1.0)], ws, algo_c=lv['cd_in'])
+                K.inorm_fwd(lv['zd'], B, hs * wsz, C, lv['eps_d'], LEAKY, lv['mean_d'], lv['istd_d'], lv['ad'], lv['rd'], ws)
             elif bn is None:
                 K.igemm(T, GEMM_S2, B, hs, wsz, src, None, lv['down_s2'], C, EPI_ACT,
-                        [K.Seg(C, out0=lv['ad'], out1=lv['rd'], slope=LEAKY)], ws, algo_c=lv['cd_in'])
+                        [K.Seg(C, out0=lv['ad'], out1=lv['rd'], bias=lv['down'].bias, slope=LEAKY)], ws,
+                        algo_c=lv['cd_in'])
             elif training:
                 K.igemm(T, GEMM_S2, B, hs, wsz, src, None, lv['down_s2'], C, EPI_Z_STATS,
                         [K.Seg(C, out0=lv['zd'], partials=lv['part_d'])], ws)
@@ -366,10 +424,22 @@ class UNetEngine(FlatParamEngine):
                 else:
                     K.igemm(T, GEMM_T2, B, hs, wsz, in0, in1, lv['up_t2'], C, EPI_FINAL,
                             [K.Seg(C, out0=lv['out'], bias=bias, final_act=fa)], ws)
+            elif lv['in_u']:
+                keep = lv['keep_u'] if self._drop_active else None
+                K.igemm(T, GEMM_T2, B, hs, wsz, in0, in1, lv['up_t2'], C, EPI_ACT,
+                        [K.Seg(C, out0=lv['zu'], bias=lv['up'].bias, slope=1.0)], ws)
+                K.inorm_fwd(lv['zu'], B, 4 * hs * wsz, C, lv['eps_u'], 0.0, lv['mean_u'], lv['istd_u'], None, lv['ru'], ws,
+                            keep=keep, keep_scale=1.0 / (1.0 - self.DROP_P))
+            elif bn is None:
+                K.igemm(T, GEMM_T2, B, hs, wsz, in0, in1, lv['up_t2'], C, EPI_ACT, [K.Seg(C, out1=lv['ru'])], ws)
+                if lv['drop'] and self._drop_active:
+                    K.dropout_apply(lv['ru'], lv['keep_u'], 1.0 / (1.0 - self.DROP_P))
             elif training:
                 K.igemm(T, GEMM_T2, B, hs, wsz, in0, in1, lv['up_t2'], C, EPI_Z_STATS,
                         [K.Seg(C, out0=lv['zu'], partials=lv['part_u'])], ws)
                 self._bn_forward(lv, 'u', bn, B * 4 * hs * wsz, lv['P_u'], lv['zu'], 0.0, None, lv['ru'])
+                if lv['drop']:            # (dropout levels are <= 8 x 8 images: an unfused pass over ru)
+                    K.dropout_apply(lv['ru'], lv['keep_u'], 1.0 / (1.0 - self.DROP_P))
             else:
                 K.bn_eval_affine(bn.weight, bn.bias, bn.running_mean, bn.running_var, BN_EPS, lv['scale_u'],
                                  lv['shift_u'])
@@ -460,19 +530,37 @@ class UNetEngine(FlatParamEngine):
         for i in range(n):
             lv = L[i]
             hs, wsz = lv['hs'], lv['ws']
+            gscale = 1.0 / (1.0 - self.DROP_P) if lv['drop'] and self._drop_active else 1.0
             if i == 0:
                 dz = lv['dz0']
+            elif lv['in_u']:
+                K.inorm_bwd(lv['Gu'], lv['zu'], lv['mean_u'], lv['istd_u'], B, 4 * hs * wsz, lv['cu_out'], gscale, ws)
+                dz = lv['Gu']
+            elif lv['bn_u'] is None:
+                dz = lv['Gu']                             # no norm: the masked gradient is dz
+                if gscale != 1.0:
+                    K.dropout_apply(dz, None, gscale)
             else:
                 self._bn_backward(lv, 'u', lv['bn_u'], B * 4 * hs * wsz, L[i - 1]['P_gu'], lv['Gu'], lv['zu'])
                 dz = lv['Gu']
+                if gscale != 1.0:                         # BatchNorm backward is linear in g: the factor rides behind it
+                    bn = lv['bn_u']
+                    for t in (dz, self._flat_slice(self.flat_g, bn.weight), self._flat_slice(self.flat_g, bn.bias)):
+                        K.dropout_apply(t, None, gscale)
+            if i > 0 and lv['up'].bias is not None:       # (instance: every transposed conv has a bias)
+                K.channel_sum(dz, B * 4 * hs * wsz, lv['cu_out'], lv['cu_out'], self._flat_slice(self.flat_g, lv['up'].bias), ws)
             in0, in1 = self._up_inputs(i)
             # (ref is only compared with 0: the LeakyReLU copy of level 0 gives the same mask as the ReLU copy)
             segs = [] if self._no_skip(i) else [K.Seg(lv['cd_out'], out0=lv['Gd'], ref=lv['skip'], slope=0.0)]
             if i < n - 1:
                 nx = L[i + 1]
-                segs.append(K.Seg(nx['cu_out'], out0=nx['Gu'], ref=nx['ru'], slope=0.0, z=nx['zu'],
-                                  mean=nx['mean_u'], istd=nx['istd_u'], partials=nx['bpart_u'],
-                                  scale=nx['scale_u'], shift=nx['shift_u']))
+                if nx['bn_u'] is None:
+                    segs.append(K.Seg(nx['cu_out'], out0=nx['Gu'], ref=nx['ru'], slope=0.0))
+                else:
+                    # (a dropped unit is a zero of ru: on a dropout level the mask must come from ref, never from z)
+                    aff = {} if nx['drop'] else dict(scale=nx['scale_u'], shift=nx['shift_u'])
+                    segs.append(K.Seg(nx['cu_out'], out0=nx['Gu'], ref=nx['ru'], slope=0.0, z=nx['zu'],
+                                      mean=nx['mean_u'], istd=nx['istd_u'], partials=nx['bpart_u'], **aff))
             if i == 0 and self.edge_path:
                 K.thin_wgrad(dz, in0, in1, B, hs, wsz, self._flat_slice(self.flat_g, lv['up'].weight), ws,
                              relu_plain0=self._skip_relu(i))
@@ -508,6 +596,11 @@ class UNetEngine(FlatParamEngine):
             hs, wsz = lv['hs'], lv['ws']
             if lv['bn_d'] is not None:
                 self._bn_backward(lv, 'd', lv['bn_d'], B * hs * wsz, L[i + 1]['P_gd'], lv['Gd'], lv['zd'])
+            elif lv['in_d']:
+                K.inorm_bwd(lv['Gd'], lv['zd'], lv['mean_d'], lv['istd_d'], B, hs * wsz, lv['cd_out'], 1.0, ws)
+            if lv['down'].bias is not None:
+                K.channel_sum(lv['Gd'], B * hs * wsz, lv['cd_out'], lv['cd_out'],
+                              self._flat_slice(self.flat_g, lv['down'].bias), ws)
             src = self.x_nhwc if i == 0 else L[i - 1]['ad']
             if i == 0 and self.edge_path:
                 if self._x_in._version != self._x_ver:

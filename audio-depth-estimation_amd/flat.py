@@ -51,7 +51,8 @@ class FlatParamEngine:
         'module', 'dtype', 'requested_dtype', 'requested_plane', 'mx8', 'model_name', 'depth_norm', 'n', 'levels', '_build',
         '_saved', 'flat_p', 'flat_g', 'flat_w16', 'fwd_serial', 'autograd_pass', 'param_meta', 'total', 'offset', 'on_grad_ready', '_shape_key', '_shape_sets', '_packed_version',
         'weights_dirty', 's2_fresh', 'train_offset', 'step_counter', 'dropout_seed', 'final_act', 'vae', 'vae_seed',
-        'vae_draws', 'eps_in', 'g_kl', 'loss_acc', 'unused_params', '_sample_k'))
+        'vae_draws', 'eps_in', 'g_kl', 'loss_acc', 'unused_params', '_sample_k', 'uses_dropout', 'batch_only', 'drop_draws',
+        '_drop_active'))
     MAX_SHAPE_SETS = 4
 
     def _shape_snapshot(self):

@@ -897,6 +897,60 @@ def dropout_mask(mask, p, seed, counter=None):
               _stream())
 
 
+# ---- InstanceNorm2d + activation (+ dropout) (csrc/inorm.hip) -------------------------------------------------
+INORM_FORMS = {1: 'resident', 2: 'streaming', 3: 'resident-plain', 4: 'streaming-plain'}
+
+
+def inorm_workspace_bytes(B, HW, Cc):
+    n = _lib.load().adn_inorm_workspace_bytes(B, HW, Cc)
+    if n < 0:
+        raise ValueError('adn_inorm_workspace_bytes: ' + _lib.load().adn_last_error().decode())
+    return n
+
+
+def inorm_form(HW, Cc, dtype):
+    """Host only: the kernel form the two launches take for this shape (a key of INORM_FORMS)."""
+    form = _lib.load().adn_inorm_form(HW, Cc, dtype_code(dtype))
+    if form < 0:
+        raise ValueError('adn_inorm_form: ' + _lib.load().adn_last_error().decode())
+    return INORM_FORMS[form]
+
+
+def inorm_fwd(z, B, HW, Cc, eps, slope, mean, istd, out_leaky, out_relu, workspace, keep=None, keep_scale=1.0):
+    """z [B, HW, Cc] (any contiguous NHWC view of it) -> mean / istd [B, Cc] and the activated copies."""
+    _dev(z, mean, istd, out_leaky, out_relu, keep, workspace)
+    _contiguous('inorm_fwd', z=z, out_leaky=out_leaky, out_relu=out_relu, keep=keep)
+    if z.numel() != B * HW * Cc or mean.numel() != B * Cc or istd.numel() != B * Cc:
+        raise RuntimeError(f'inorm_fwd: z {tuple(z.shape)} / mean {tuple(mean.shape)} for B={B}, HW={HW}, C={Cc}')
+    for t in (out_leaky, out_relu):
+        if t is not None and (t.numel() != z.numel() or t.dtype != z.dtype):
+            raise RuntimeError('inorm_fwd: an output does not match z')
+    if keep is not None and (keep.numel() != z.numel() or keep.dtype != torch.uint8):
+        raise RuntimeError('inorm_fwd: keep must be a uint8 mask of the shape of z')
+    _lib.call('adn_inorm_fwd', ptr(z), B, HW, Cc, dtype_code(z.dtype), float(eps), float(slope), ptr(mean), ptr(istd),
+              ptr(out_leaky), ptr(out_relu), ptr(keep), float(keep_scale), ptr(workspace), _nbytes(workspace), _stream())
+
+
+def dropout_apply(x, keep, scale):
+    """x <- x * (keep ? scale : 0) in place; keep None: x * scale."""
+    _dev(x, keep)
+    _contiguous('dropout_apply', x=x, keep=keep)
+    if keep is not None and (keep.numel() != x.numel() or keep.dtype != torch.uint8):
+        raise RuntimeError('dropout_apply: keep must be a uint8 mask of the shape of x')
+    _lib.call('adn_dropout_apply', ptr(x), ptr(keep), x.numel(), dtype_code(x.dtype), float(scale), _stream())
+
+
+def inorm_bwd(g, z, mean, istd, B, HW, Cc, gscale, workspace):
+    """g (masked upstream gradient, same layout and dtype as z) <- dz, in place."""
+    _dev(g, z, mean, istd, workspace)
+    _contiguous('inorm_bwd', g=g, z=z)
+    if z.numel() != B * HW * Cc or g.numel() != z.numel() or g.dtype != z.dtype or mean.numel() != B * Cc \
+            or istd.numel() != B * Cc:
+        raise RuntimeError(f'inorm_bwd: g {tuple(g.shape)} / z {tuple(z.shape)} for B={B}, HW={HW}, C={Cc}')
+    _lib.call('adn_inorm_bwd', ptr(g), ptr(z), ptr(mean), ptr(istd), B, HW, Cc, dtype_code(z.dtype), float(gscale),
+              ptr(workspace), _nbytes(workspace), _stream())
+
+
 def _vae_shapes(who, B, Cc, L, **named):
     """Every operand of the VAE kernels must hold exactly its [rows, cols] (contiguous): the kernels index by B, C, L."""
     for name, (t, numel) in named.items():

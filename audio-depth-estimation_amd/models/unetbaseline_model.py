@@ -9,7 +9,8 @@ star import (train.py:5-7, :421).  The nn.Module tree (and therefore every state
 ``model.model.1.model.2.running_var``) is identical to the reference so checkpoints interchange;
 the arithmetic is NOT torch's: UnetGenerator.forward hands the whole network to the fused HIP
 pipeline in engine.py (implicit-GEMM MFMA convolutions with BatchNorm/activation/skip-concat fused
-around them).  There is no CPU path: calling the model with CPU tensors raises RuntimeError.
+around them; norm='instance' / 'none' and use_dropout=True run there too, csrc/inorm.hip).  There is no CPU path:
+calling the model with CPU tensors raises RuntimeError.
 """
 import functools
 import os
@@ -194,14 +195,19 @@ class UnetGenerator(nn.Module):
         levels, blk = [], self.model
         while blk is not None:
             parts = blk._parts()
-            for bn in (parts['bn_d'], parts['bn_u']):
-                if bn is not None and not isinstance(bn, nn.BatchNorm2d):
-                    raise NotImplementedError('the fused libadn pipeline implements norm="batch" (the only '
-                                              'setting train.py/test.py use)')
-            if parts['dropout']:
-                raise NotImplementedError('use_dropout=True is not on the hot path (every reference caller '
-                                          'passes False)')
-            levels.append({k: parts[k] for k in ('down', 'up', 'bn_d', 'bn_u')})
+            lv = dict(down=parts['down'], up=parts['up'], drop=parts['dropout'])
+            # per norm slot: the BatchNorm2d module (or None) and whether an InstanceNorm2d stands there; Identity
+            # (norm='none') and the slots without a norm layer are (None, False)
+            for tag in ('d', 'u'):
+                m = parts['bn_' + tag]
+                inorm = isinstance(m, nn.InstanceNorm2d)
+                if inorm and (m.affine or m.track_running_stats):
+                    raise NotImplementedError('the fused libadn pipeline implements InstanceNorm2d(affine=False, '
+                                              'track_running_stats=False), what get_norm_layer("instance") builds')
+                lv['bn_' + tag] = m if isinstance(m, nn.BatchNorm2d) else None
+                lv['in_' + tag] = inorm
+                lv['eps_' + tag] = m.eps if inorm else None
+            levels.append(lv)
             blk = parts['sub']
         return levels
 

@@ -32,9 +32,12 @@ def build_parser():
                    help='accepted for command-line compatibility (reference test.py:36); PNG panels are not produced')
     p.add_argument('--output_dir', type=str, default='./val/')
     p.add_argument('--vis_batch_size', type=int, default=4, help='accepted and ignored (reference test.py:40)')
-    p.add_argument('--precision', default='bf16', choices=['bf16', 'f32'])
-    p.add_argument('--synthetic', type=int, default=0)
-    p.add_argument('--batch_size', type=int, default=None)
+    g = p.add_argument_group('MI355X')
+    g.add_argument('--precision', default='bf16', choices=['bf16', 'f32'])
+    g.add_argument('--synthetic', type=int, default=0)
+    g.add_argument('--batch_size', type=int, default=None)
+    g.add_argument('--norm', default='batch', choices=['batch', 'instance', 'none'],
+                   help='norm layer the checkpoint was trained with (train.py --norm)')
     return p
 
 
@@ -88,7 +91,7 @@ def main(argv=None):
     print(f'Eval Dataset of {len(eval_set)} instances')
     loader = DataLoader(eval_set, batch_size=cfg.mode.batch_size, shuffle=False, num_workers=cfg.mode.num_threads)
 
-    model = define_G(cfg, input_nc=2, output_nc=1, ngf=64, netG=cfg.model.generator, norm='batch', use_dropout=False,  # noqa: F405
+    model = define_G(cfg, input_nc=2, output_nc=1, ngf=64, netG=cfg.model.generator, norm=args.norm, use_dropout=False,  # noqa: F405
                      init_type='normal', init_gain=0.02, gpu_ids=[])
     model.compute_dtype = torch.bfloat16 if args.precision == 'bf16' else torch.float32
     path, exp, epoch = resolve_checkpoint(args, cfg)

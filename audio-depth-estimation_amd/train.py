@@ -7,7 +7,8 @@ layout (:600-606, :897-909, :1006-1017: {'epoch','state_dict','optimizer'} under
 Differences, all on the device side: the step runs in engine.FusedTrainer (HIP kernels, optional hipGraph),
 the audio front-end runs per BATCH on the device (GpuAudioFrontend), validation metrics are one device
 kernel per batch, and multi-GPU is one process per GPU (torchrun) with RCCL all-reduce instead of
-nn.DataParallel.  Extra flags: --precision {bf16,f32}, --synthetic N (no dataset needed), --graph.
+nn.DataParallel.  Extra flags: --precision {bf16,f32}, --synthetic N (no dataset needed), --graph, --norm {batch,instance,none},
+--use_dropout.
 wandb / PNG visualisation / sequence hold-out plumbing of the reference are logging-only and out of scope.
 
     python -m audio_depth_estimation_amd.train --dataset batvisionv2 --batch_size 32
@@ -86,6 +87,9 @@ def build_parser():
     g.add_argument('--synthetic', type=int, default=0, help='train on N synthetic items (no dataset on disk)')
     g.add_argument('--epochs', type=int, default=None)
     g.add_argument('--graph', action='store_true', help='replay the step as one hipGraph (single GPU)')
+    g.add_argument('--norm', default='batch', choices=['batch', 'instance', 'none'],
+                   help='norm layer of define_G (instance: per-sample statistics, for per-GPU batches of 1 or 2)')
+    g.add_argument('--use_dropout', action='store_true', help='Dropout(0.5) in the intermediate 512-channel blocks')
     return p
 
 
@@ -116,6 +120,10 @@ def experiment_name(cfg, args):
         name += '_IMG'
     if args.max_depth is not None and args.max_depth != 30.0:
         name += f'_MD{int(args.max_depth)}'
+    if getattr(args, 'norm', 'batch') != 'batch':
+        name += '_' + args.norm
+    if getattr(args, 'use_dropout', False):
+        name += '_drop'
     return name + '_' + cfg.mode.experiment_name
 
 
@@ -221,7 +229,8 @@ def main(argv=None):
     train_loader, val_loader, fe, sampler = make_loaders(cfg, args, rank, world)
 
     input_nc = 3 if args.eval_img else 2
-    model = define_G(cfg, input_nc=input_nc, output_nc=1, ngf=64, netG='unet_256', norm='batch', use_dropout=False,  # noqa: F405
+    model = define_G(cfg, input_nc=input_nc, output_nc=1, ngf=64, netG='unet_256', norm=args.norm,  # noqa: F405
+                     use_dropout=args.use_dropout,
                      init_type='normal', init_gain=0.02, gpu_ids=[])
     model.compute_dtype = torch.bfloat16 if args.precision == 'bf16' else torch.float32
     model = model.to(device).train()
@@ -231,6 +240,9 @@ def main(argv=None):
         ck = torch.load(os.path.join(ckpt_dir, f'checkpoint_{cfg.mode.checkpoints}.pth'), map_location=device)
         model.load_state_dict({k[7:] if k.startswith('module.') else k: v for k, v in ck['state_dict'].items()})
         start_epoch = ck['epoch'] + 1
+    if world > 1 and (args.norm != 'batch' or args.use_dropout):
+        raise NotImplementedError('--norm instance / none and --use_dropout train on one GPU (the data-parallel step is '
+                                  'wired for norm="batch" without dropout)')
     reducer = addp.GradientAllReducer() if world > 1 else None
     max_depth = cfg.dataset.max_depth if cfg.dataset.max_depth else 30.0
     trainer = FusedTrainer(model.engine(), crit, l1w, sw, lam, max_depth=max_depth, optimizer=cfg.mode.optimizer,

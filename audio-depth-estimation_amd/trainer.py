@@ -233,6 +233,9 @@ class FusedTrainer(OptimTail):
     def __init__(self, engine, criterion='Combined', l1_weight=0.5, silog_weight=0.5, silog_lambda=0.5,
                  max_depth=30.0, optimizer='AdamW', lr=0.002, betas=(0.9, 0.999), eps=1e-8, weight_decay=None,
                  clip_norm=1.0, mask_mode='ne0', ddp=None):
+        if ddp is not None and not getattr(engine, 'batch_only', True):
+            raise NotImplementedError('data-parallel training is wired for norm="batch" without dropout only '
+                                      '(norm="instance" / "none" and use_dropout=True train on one GPU)')
         self._init_optim(engine, optimizer, lr, betas, eps, weight_decay, clip_norm, ddp)
         self.criterion = self.CRIT[criterion]
         self.l1_weight, self.silog_weight, self.silog_lambda = float(l1_weight), float(silog_weight), float(silog_lambda)
@@ -259,6 +262,8 @@ class FusedTrainer(OptimTail):
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
         self.loss_ws = torch.empty(4096 + 8, **f64)
         self.gout = None
+        if getattr(self.engine, 'uses_dropout', False):
+            self.engine.step_counter = self.state     # device step count: a replayed step draws fresh dropout masks
 
     def step(self, audio, gt):
         return self._graphed(audio, gt)

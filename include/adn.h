@@ -466,6 +466,33 @@ int adn_bn_bwd_apply(void* g, const void* z, int64_t pixels, int32_t C, int32_t 
                      const float* scale, const float* mean, const float* istd, const float* coef,
                      void* stream);
 
+/* InstanceNorm2d(affine=False, track_running_stats=False) (get_norm_layer('instance'), unetbaseline_model.py:70-71; the
+ * reference's default norm) and nn.Dropout(0.5) (:227) around it.  z [B][HW][C] in dtype is the raw conv output WITH its
+ * bias; statistics are per (sample, channel) over the HW rows, biased variance taken about the mean (two passes on chip,
+ * or per-slab (mean, M2) merged in slab order), fixed summation order, no atomics.  Train and eval are the same call.
+ *   adn_inorm_fwd: mean / istd [B][C] f32 for the backward; out_leaky = leaky(xhat, slope) and / or out_relu =
+ *     relu(xhat), xhat = (z - mean) * istd (either may be NULL, as adn_bn_act).  keep (optional): uint8 [B][HW][C] keep
+ *     mask of adn_dropout_mask; the outputs are multiplied by keep ? keep_scale : 0.
+ *   adn_inorm_bwd: g holds the upstream gradient already masked by the activation (ADN_EPI_BWD without partials, ref =
+ *     the activated tensor) and is overwritten with dz = istd * (g' - mean_hw(g') - xhat * mean_hw(g' * xhat)),
+ *     g' = gscale * g (gscale = 1 / (1 - p) on a dropout level: the ref > 0 mask has already zeroed the dropped units).
+ * Two forms chosen on the host (adn_inorm_form: 1 resident, 2 streaming; + 2 when C % 8 != 0 runs one element per access
+ * and not 16 bytes): resident keeps a workgroup's slice of one sample in LDS and reads z (backward: g and z) once;
+ * streaming runs a statistics pass over slabs of rows and an apply pass.  workspace: adn_inorm_workspace_bytes, checked by
+ * both launches whatever the form.  HW < 2 (torch: "Expected more than 1 spatial element"), NULL or misaligned pointers
+ * (16 bytes for the activations when C % 8 == 0, 8 for keep), a short workspace: ADN_ERR_ARG, nothing launched. */
+/* nn.Dropout around a BatchNorm or no norm (the instance-norm launches take the mask themselves): x (dtype, n elements)
+ * <- x * (keep ? scale : 0) in place; keep NULL: x * scale (the uniform 1 / (1 - p) of the backward pass). */
+int adn_dropout_apply(void* x, const uint8_t* keep, int64_t n, int32_t dtype, float scale, void* stream);
+int64_t adn_inorm_workspace_bytes(int32_t B, int32_t HW, int32_t C);
+int adn_inorm_form(int32_t HW, int32_t C, int32_t dtype);
+int adn_inorm_fwd(const void* z, int32_t B, int32_t HW, int32_t C, int32_t dtype, float eps, float slope,
+                  float* mean, float* istd, void* out_leaky, void* out_relu, const uint8_t* keep,
+                  float keep_scale, void* workspace, int64_t workspace_bytes, void* stream);
+int adn_inorm_bwd(void* g, const void* z, const float* mean, const float* istd, int32_t B, int32_t HW,
+                  int32_t C, int32_t dtype, float gscale, void* workspace, int64_t workspace_bytes,
+                  void* stream);
+
 /* Masked depth loss (train.py:646-669, utils_loss.py:29-49).
  * stats[0..4) (f64) = N, sum|p-g|, sum d, sum d^2 over valid pixels; mask_mode 0: gt != 0, 1: gt > 0,
  * 2: every element (inputs already gathered, utils_loss.py call sites).
