@@ -460,6 +460,8 @@ extern "C" int adn_optimizer_step(float* params, const float* grads, float* exp_
   ADN_CHECK_ARG(((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) |
                   reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0,
                 "adn_optimizer_step: buffers must be 16-byte aligned");
+  ADN_CHECK_ARG((reinterpret_cast<uintptr_t>(bf16_copy) & 7) == 0,      // written four elements (8 bytes) per store
+                "adn_optimizer_step: bf16_copy must be 8-byte aligned");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(optimizer_advance_kernel, dim3(1), dim3(64), 0, st, state, (double)beta1, (double)beta2);
   ADN_CHECK_LAUNCH();

@@ -92,6 +92,10 @@ class UNetEngine(FlatParamEngine):
         """
         T = self.dtype
         fresh = self._mirror_fresh()
+        if T == torch.bfloat16 and not fresh:
+            # the whole mirror, not only the conv ranges the S2 operands view: afterwards flat_w16 == bf16(flat_p)
+            # everywhere, whoever changed the parameters (a torch copy: part of a launch plan as a Python action)
+            _lib.record_py(lambda: self.flat_w16.copy_(self.flat_p))
         for lv in self.levels:
             for key in ('down', 'up'):
                 w = lv[key].weight
@@ -102,10 +106,8 @@ class UNetEngine(FlatParamEngine):
                     K.pack_weights(master, X, Y, T, lv[key + '_s2'], None, y_pad=ypad)
                 elif T == torch.float32:
                     lv[key + '_s2'] = master                       # channels_last memory == S2 operand
-                elif not fresh:
-                    K.pack_weights(master, X, Y, T, lv[key + '_s2'], None)
         # source of the T2 pack: the bf16 mirror when the fused optimizer has just written ALL of it (half the read
-        # traffic, identical values); the f32 masters otherwise (the re-cast above skips the padded edge layers)
+        # traffic, identical values); the f32 masters otherwise
         src = self.flat_w16 if (T == torch.bfloat16 and fresh) else self.flat_p
         K.pack_t2_multi(src, self.t2_table, self.t2_layers, self.t2_blocks, T, self.t2_all)
         self.weights_dirty = False

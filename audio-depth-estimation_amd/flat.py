@@ -158,3 +158,13 @@ class FlatParamEngine:
         """True when the bf16 parameter mirror written by the fused optimizer still matches the f32 masters: nobody
         (load_state_dict, an in-place edit) touched the parameters since the last pack."""
         return self.s2_fresh and self._packed_version == self._version_sum()
+
+    def resync_mirror(self):
+        """After a change of the parameters from outside: re-cast the whole bf16 mirror from the f32 masters now and mark
+        it fresh, so that the next pack (the one a re-capture of the step records) reads it like a mirror the optimizer
+        has just written.  The packed operands themselves stay dirty."""
+        if self.flat_w16 is not None:
+            self.flat_w16.copy_(self.flat_p)
+            self.s2_fresh = True
+        self.weights_dirty = True
+        self._packed_version = self._version_sum()

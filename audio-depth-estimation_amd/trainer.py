@@ -14,7 +14,8 @@ class GraphedStep:
     host): after ``after_steps`` eager steps it is captured over static input buffers, either into ONE hipGraph
     (``enable_graph``) or as a launch plan, the list of prebuilt ctypes calls that ``_lib.replay`` walks
     (``_plan_after``), and replayed from then on.  Subclasses implement ``_step_impl(*inputs)`` (inputs may be None)
-    and return device tensors that stay valid across replays; ``engine`` has weights_dirty / s2_fresh / pin_buffers.
+    and return device tensors that stay valid across replays; ``engine`` has weights_dirty / s2_fresh / pin_buffers, and,
+    where it keeps packed copies of its parameters, _packed_version / _version_sum() / resync_mirror() (FlatParamEngine).
     Setting ``_plan, _plan_after = None, None`` drops a plan: the step is eager again and can be re-armed."""
     _graph = _graph_after = _plan = _plan_after = None
     _calls = 0
@@ -28,6 +29,17 @@ class GraphedStep:
 
     def _graphed(self, *inputs):
         self._calls += 1
+        eng = self.engine
+        versions = getattr(eng, '_version_sum', None)       # (an engine that packs no operand copies tracks no versions)
+        if (self._plan is not None or self._graph is not None) and versions is not None \
+                and eng._packed_version != versions():
+            # somebody changed the parameters from outside since the engine last packed them (load_state_dict, an
+            # in-place edit, a torch.optim step): the captured step holds the pack decisions of the step it was
+            # recorded from (no re-cast of the bf16 mirror, T2 operands read from it) and would run on the old
+            # operands.  Drop it; this very call captures again, over a mirror re-cast here, once, so that the new
+            # capture records the same fast path (not a re-cast on every replay).
+            self._graph = self._plan = None
+            eng.resync_mirror()
         if self._plan is not None or self._graph is not None:
             for buf, t in zip(self._g_in, inputs):
                 if (buf is None) != (t is None) or (buf is not None and buf.shape != t.shape):

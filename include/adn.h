@@ -601,7 +601,9 @@ int adn_grad_norm_ranges(const float* grads, const int64_t* ranges, int32_t n_ra
                          int32_t n_extra, float max_norm, double* state, void* workspace, int64_t workspace_bytes,
                          void* stream);
 /* kind: 0 AdamW (decoupled decay), 1 Adam (L2 in gradient), 2 SGD. Advances state[0..2].
- * bf16_copy (optional, n bf16): mirror of the updated parameters, i.e. next step's S2 GEMM operands. */
+ * bf16_copy (optional, n bf16): mirror of the updated parameters, i.e. next step's S2 GEMM operands.
+ * params, grads and the moments must be 16-byte aligned, bf16_copy 8-byte aligned (NULL: no mirror); a call that
+ * breaks this is refused before anything is launched. */
 int adn_optimizer_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
                        int64_t n, int32_t kind, float lr, float beta1, float beta2, float eps,
                        float weight_decay, int32_t use_clip, double* state, void* bf16_copy,

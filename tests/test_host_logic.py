@@ -345,9 +345,17 @@ def test_launch_plan_capture_and_replay_state_machine():
 
     class Engine:
         weights_dirty, s2_fresh, pins = False, False, 0
+        _packed_version, version, resyncs = 0, 0, 0          # ``version``: bumped by an edit of the parameters from outside
 
         def pin_buffers(self):
             self.pins += 1
+
+        def _version_sum(self):
+            return self.version
+
+        def resync_mirror(self):
+            self.resyncs += 1
+            self.weights_dirty, self.s2_fresh, self._packed_version = True, True, self.version
 
     class Step(GraphedStep):
         def __init__(self):
@@ -404,6 +412,19 @@ def test_launch_plan_capture_and_replay_state_machine():
             assert all(g is h for g, h in zip(t._g_in, bufs)) and not torch.equal(t._g_in[0][:4], a[:4])
         a, b, c = mk(50), (mk(51) if with_b else None), mk(52)
         assert float(t._graphed(a, b, c)[0]) == value(a, b, c) and t.impl_calls == n      # the plan still replays
+        # the parameters changed from outside since the engine packed them: the plan holds the pack decisions of the step
+        # it recorded, so it is dropped and recorded again by the same call, over a mirror re-cast once
+        eng.version += 1
+        a, b, c = mk(53), (mk(54) if with_b else None), mk(55)
+        assert float(t._graphed(a, b, c)[0]) == value(a, b, c)
+        n += 1
+        assert t.impl_calls == n and t._plan is not None and t._plan is not plan and eng.pins == 2 and eng.resyncs == 1
+        assert eng._packed_version == eng.version and t._g_in[0] is not bufs[0]
+        a, b, c = mk(56), (mk(57) if with_b else None), mk(58)
+        assert float(t._graphed(a, b, c)[0]) == value(a, b, c) and t.impl_calls == n      # ... and replays from then on
+        assert eng.resyncs == 1
+        plan, bufs = t._plan, list(t._g_in)
+        eng.pins = 1
         # dropping the plan: eager again, and it can be re-armed
         t._plan, t._plan_after = None, None
         for i in range(2):
