@@ -18,8 +18,7 @@ from typing import NamedTuple
 import torch
 
 from . import kernels as K
-from ._lib import EPI_ACT, EPI_FINAL, EPI_RAW, GEMM_S2, GEMM_T2
-from .engine import BN_EPS, LEAKY, FusedTrainer, UNetEngine
+from .engine import FusedTrainer, UNetEngine
 
 
 class CVAEEngine(UNetEngine):
@@ -147,67 +146,33 @@ class CVAEEngine(UNetEngine):
                 self.weights_dirty, self.s2_fresh, self._packed_version = flags
 
     def _sample(self, x, Kn, mode, eps, seed):
-        self._prepare(x)
-        T, B, n, L, ws = self.dtype, self.B, self.n, self.levels, self.workspace
+        self._begin(x)
         if seed is not None:
             call_seed = (int(seed) * 0x9E3779B97F4A7C15 + 0x632BE59BD9B4E019) & 0xFFFFFFFFFFFFFFFF
         else:
             call_seed = self.vae_seed ^ (((self.vae_draws + 1) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF)
             if eps is None and mode == 'sample':
                 self.vae_draws += Kn
-        if self.weights_dirty or self._packed_version != self._version_sum():
-            self._pack_weights()
-        if not self.edge_path:
-            K.nchw_to_nhwc(x, self.x_nhwc)
+        B, n, L = self.B, self.n, self.levels
         # ---- down path, once, BatchNorm in eval form
-        for i, lv in enumerate(L):
-            src = self.x_nhwc if i == 0 else L[i - 1]['ad']
-            C, hs, wsz = lv['cd_out'], lv['hs'], lv['ws']
-            bn = lv['bn_d']
-            seg = dict(out0=lv['ad'], out1=lv['rd'], slope=LEAKY)
-            if self._vae_level(i):
-                K.igemm(T, GEMM_S2, B, hs, wsz, src, None, lv['down_s2'], C, EPI_RAW, [K.Seg(C, out0=self.vae_h)], ws)
-            elif i == 0 and self.edge_path:
-                K.l0_forward(x, self._flat_slice(self.flat_p, lv['down'].weight), B, hs, wsz, LEAKY, lv['ad'], lv['rd'])
-            elif bn is None:
-                K.igemm(T, GEMM_S2, B, hs, wsz, src, None, lv['down_s2'], C, EPI_ACT, [K.Seg(C, **seg)], ws,
-                        algo_c=lv['cd_in'])
-            else:
-                K.bn_eval_affine(bn.weight, bn.bias, bn.running_mean, bn.running_var, BN_EPS, lv['scale_d'],
-                                 lv['shift_d'])
-                K.igemm(T, GEMM_S2, B, hs, wsz, src, None, lv['down_s2'], C, EPI_ACT,
-                        [K.Seg(C, scale=lv['scale_d'], shift=lv['shift_d'], **seg)], ws)
+        for i in range(n):
+            self._down_conv(i, x, False)
         # ---- bottleneck: mu / logvar once, K draws, the innermost rd operand for all K * B rows
         fp = [self._flat_slice(self.flat_p, p) for p in self._vae_params()]
         K.vae_sample(self.vae_h, *fp, call_seed, eps, self.vae_mu, self.vae_logvar, self.s_eps, self.s_z, self.vae_kl_img,
                      self.vae_kl, self.s_rd, mode=K.VAE_MEAN if mode == 'mean' else K.VAE_DRAW)
-        # ---- up path: per draw, at batch B (the launches of forward(): same plans, same workspace), skips shared
+        # ---- up path: forward()'s walk per draw, at batch B, skips shared; the eval affines once for all draws
         for lv in L[1:]:
-            bn = lv['bn_u']
-            K.bn_eval_affine(bn.weight, bn.bias, bn.running_mean, bn.running_var, BN_EPS, lv['scale_u'], lv['shift_u'])
+            self._eval_affine(lv['u'])
         l0 = L[0]
         out = torch.empty(Kn * B, 2 * l0['hs'], 2 * l0['ws'], l0['cu_out'], dtype=torch.float32, device=x.device)
         for k in range(Kn):
             rows = slice(k * B, (k + 1) * B)
             for i in reversed(range(n)):
-                lv = L[i]
                 in0, in1 = (self.s_rd[rows], None) if i == n - 1 else self._up_inputs(i)
-                C, hs, wsz = lv['cu_out'], lv['hs'], lv['ws']
-                if i > 0:
-                    K.igemm(T, GEMM_T2, B, hs, wsz, in0, in1, lv['up_t2'], C, EPI_ACT,
-                            [K.Seg(C, out1=lv['ru'], scale=lv['scale_u'], shift=lv['shift_u'])], ws)
-                elif self.n1_path:
-                    K.convt_n1_forward(T, B, hs, wsz, in0, in1, self._flat_slice(self.flat_p, lv['up'].weight),
-                                       lv['up'].bias, self.final_act, out[rows], ws, relu_in0=self._skip_relu(i))
-                else:
-                    K.igemm(T, GEMM_T2, B, hs, wsz, in0, in1, lv['up_t2'], C, EPI_FINAL,
-                            [K.Seg(C, out0=out[rows], bias=lv['up'].bias, final_act=self.final_act)], ws)
-        H, W, Cout = out.shape[1], out.shape[2], out.shape[3]
-        if Cout == 1:
-            samples = out.view(Kn, B, 1, H, W)
-        else:
-            samples = torch.empty(Kn, B, Cout, H, W, dtype=torch.float32, device=out.device)
-            K.nhwc_to_nchw(out, samples.view(Kn * B, Cout, H, W))
+                self._up_conv(i, in0, in1, out[rows], False, affine=False)
+        samples = self._nchw(out)
+        samples = samples.view(Kn, B, *samples.shape[1:])
         mean, std = torch.empty_like(samples[0]), torch.empty_like(samples[0])
         K.sample_stats(samples, mean, std)
         return SampleResult(samples, mean, std, self.vae_mu.clone(), self.vae_logvar.clone(), self.vae_kl[0].clone(),

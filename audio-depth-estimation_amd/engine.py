@@ -32,6 +32,31 @@ BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
 LEAKY = 0.2
 
+THIN, GROUP, MULTI, OWN = 'thin', 'group', 'multi', 'own'      # routes of a weight gradient (UNetEngine._emit_wgrad)
+
+
+class Side:
+    """One conv layer of a U-Net level as the walks see it: 'd' the strided conv, 'u' the transposed conv.
+    Built per input shape by UNetEngine._prepare; the level dict holds them as lv['d'] and lv['u']."""
+    __slots__ = ('tag', 'conv', 'X', 'Y', 'ypad', 'C', 'hs', 'ws', 'px',        # layer: weight [X, Y, 4, 4], Y padded to ypad
+                 'norm', 'bn', 'eps', 'drop',                                   # 'batch' | 'instance' | 'none' behind it
+                 'z', 'mean', 'istd', 'scale', 'shift', 'coef', 'part', 'bpart',
+                 'P', 'Pg', 'Pb', 's2', 't2', 't2_off',                         # partial rows: forward, own dgrad, of bpart
+                 'wshape', 'c_valid', 'route', 'trigger', 'patch_ok', 'wclass', 'wq', 'sq')
+
+    def __init__(self, tag, conv, hs, ws, ypad, bn, inorm, eps, drop=False):
+        for k in self.__slots__:
+            setattr(self, k, None)
+        self.tag, self.conv, self.hs, self.ws, self.bn, self.eps, self.drop = tag, conv, hs, ws, bn, eps, drop
+        self.X, self.Y = conv.weight.shape[0], conv.weight.shape[1]
+        self.ypad = self.Y if ypad is None else ypad              # gathered channels as the kernels see them
+        self.C = self.X if tag == 'd' else self.Y                 # output channels and pixels per image
+        self.px = hs * ws if tag == 'd' else 4 * hs * ws
+        self.norm = 'batch' if bn is not None else 'instance' if inorm else 'none'
+        self.c_valid = self.Y if self.ypad != self.Y else 0
+        self.P = self.Pg = self.Pb = self.wclass = self.wq = 0
+        self.route, self.trigger, self.patch_ok = OWN, False, False
+
 
 class UNetEngine(FlatParamEngine):
     """Runs UnetGenerator.forward/backward through libadn.  One engine per module instance."""
@@ -96,16 +121,9 @@ class UNetEngine(FlatParamEngine):
             # the whole mirror, not only the conv ranges the S2 operands view: afterwards flat_w16 == bf16(flat_p)
             # everywhere, whoever changed the parameters (a torch copy: part of a launch plan as a Python action)
             _lib.record_py(lambda: self.flat_w16.copy_(self.flat_p))
-        for lv in self.levels:
-            for key in ('down', 'up'):
-                w = lv[key].weight
-                X, Y = w.shape[0], w.shape[1]
-                master = self._flat_slice(self.flat_p, w)
-                ypad = lv[key + '_ypad']
-                if ypad != Y:
-                    K.pack_weights(master, X, Y, T, lv[key + '_s2'], None, y_pad=ypad)
-                elif T == torch.float32:
-                    lv[key + '_s2'] = master                       # channels_last memory == S2 operand
+        for s in self._sides():
+            if s.ypad != s.Y:
+                K.pack_weights(self._flat_slice(self.flat_p, s.conv.weight), s.X, s.Y, T, s.s2, None, y_pad=s.ypad)
         # source of the T2 pack: the bf16 mirror when the fused optimizer has just written ALL of it (half the read
         # traffic, identical values); the f32 masters otherwise
         src = self.flat_w16 if (T == torch.bfloat16 and fresh) else self.flat_p
@@ -115,10 +133,40 @@ class UNetEngine(FlatParamEngine):
         self._packed_version = self._version_sum()
 
     # ------------------------------------------------------------------ buffers
+    def _sides(self):
+        """Every conv layer's Side, in parameter order of the level list: down then up, outermost level first."""
+        return [lv[tag] for lv in self.levels for tag in ('d', 'u')]
+
     def _prepare(self, x):
         if not self._bound():
             self.bind_parameters()
+        self._check_input(x)
+        key = self._buffer_key(x)
+        if self._shape_enter(key):
+            return
         B, Cin, H, W = x.shape
+        dev = x.device
+        self._decide_edge_paths(Cin, W)
+        self._build_sides(H, W)
+        ws_bytes = self._query_plans(B)
+        self._alloc_activations(B, H, W, dev)
+        self._build_t2(dev)
+        ws_bytes = max(ws_bytes, self._group_patch_launches(B))
+        self._prepare_fused_norm(B, dev)
+        for lv in self.levels:        # the names tests and tools read a layer's operands by; the engine reads the Side
+            d, u = lv['d'], lv['u']
+            lv.update(down_ypad=d.ypad, up_ypad=u.ypad, down_s2=d.s2, up_s2=u.s2, down_t2=d.t2, up_t2=u.t2,
+                      down_sq=d.sq, up_sq=u.sq)
+        if self.vae is not None:
+            self._prepare_vae(B, dev)
+        self.workspace = torch.empty(ws_bytes // 4 + 4, dtype=torch.float32, device=dev)
+        self.red_ws = torch.empty(4096, dtype=torch.float64, device=dev)
+        self.weights_dirty = True
+        self._shape_key = key
+        self.B = B
+
+    def _check_input(self, x):
+        B, _, H, W = x.shape
         n = self.n
         # (torch raises this from the first InstanceNorm2d that sees a 1 x 1 image, before the conv below it fails)
         for i, lv in enumerate(self.levels):
@@ -129,14 +177,11 @@ class UNetEngine(FlatParamEngine):
         if H % (1 << n) or W % (1 << n):
             raise RuntimeError(f'input {H}x{W} is not divisible by 2^{n}: Kernel size can\'t be greater than '
                                f'actual input size')
-        key = self._buffer_key(x)
-        if self._shape_enter(key):
-            return
-        dev, T = x.device, self.dtype
-        f32 = dict(dtype=torch.float32, device=dev)
-        ws_bytes = 16
+
+    def _decide_edge_paths(self, Cin, W):
+        """How the two thin outermost layers run: cin_pad / cout_pad, n1_path, edge_path, skip0_leaky."""
+        T, l0 = self.dtype, self.levels[0]
         epc = 8 if T == torch.bfloat16 else 4          # elements per 16-byte chunk
-        l0 = self.levels[0]
         # Edge layers: the first conv (Cin = 2) and the last transposed conv (Cout = 1) run on the MFMA
         # kernels with their thin channel dimension zero-padded to one 16-byte chunk.
         self.cin_pad = Cin
@@ -149,7 +194,7 @@ class UNetEngine(FlatParamEngine):
         # Dedicated HBM-bound kernels for the thin outermost layers (csrc/edge.hip; bf16 path, the unet_256 / ngf 64
         # geometry): first conv 2 -> 64 forward + weight gradient, last transposed conv 128 -> 1 input / weight gradient.
         # They read the thin operand (network input, output gradient) as planar f32: no channel padding at all.
-        self.edge_path = (T == torch.bfloat16 and self.n1_path and n >= 2 and Cin == 2
+        self.edge_path = (T == torch.bfloat16 and self.n1_path and self.n >= 2 and Cin == 2
                           and l0['down'].weight.shape[0] == 64 and cu_in0 == 128 and l0['bn_d'] is None
                           and self.batch_only and l0['down'].bias is None
                           and (W // 2) % 32 == 0 and not os.environ.get('ADN_NO_EDGE'))
@@ -160,143 +205,147 @@ class UNetEngine(FlatParamEngine):
         # slope), so rd[0] is neither allocated nor written.  ADN_L0_TWO_COPIES=1 keeps the separate ReLU copy (A/B).
         self.skip0_leaky = (self.edge_path and self.n1_path and not self._no_skip(0)
                             and not os.environ.get('ADN_L0_TWO_COPIES'))
-        self.x_nhwc = None if self.edge_path else torch.empty(B, H, W, self.cin_pad, dtype=T, device=dev)
-        batching_patch = (T == torch.bfloat16 and not os.environ.get('ADN_NO_WGRAD_BATCH')
-                          and not os.environ.get('ADN_NO_PATCH_BATCH'))
-        pshape_d, pshape_u = {}, {}
+
+    def _build_sides(self, H, W):
+        """The two Side records of every level: layer geometry, norm kind, weight-gradient problem."""
         for i, lv in enumerate(self.levels):
-            dw, uw = lv['down'].weight, lv['up'].weight
-            cd_in, cd_out = dw.shape[1], dw.shape[0]
-            cu_in, cu_out = uw.shape[0], uw.shape[1]
             hs, wsz = H >> (i + 1), W >> (i + 1)
-            lv.update(hs=hs, ws=wsz, cd_in=cd_in, cd_out=cd_out, cu_in=cu_in, cu_out=cu_out)
-            cd_in_p = self.cin_pad if i == 0 else cd_in          # gathered channels as the kernels see them
-            cu_out_p = self.cout_pad if i == 0 else cu_out
-            lv.update(down_ypad=cd_in_p, up_ypad=cu_out_p)
-            act = lambda c, h=hs, w_=wsz: torch.empty(B, h, w_, c, dtype=T, device=dev)
-            lv['ad'] = act(cd_out) if i < n - 1 else None
-            lv['rd'] = None if self._no_skip(i) or (i == 0 and self.skip0_leaky) else act(cd_out)
+            d = Side('d', lv['down'], hs, wsz, self.cin_pad if i == 0 else None, lv['bn_d'], lv['in_d'], lv['eps_d'])
+            u = Side('u', lv['up'], hs, wsz, self.cout_pad if i == 0 else None, lv['bn_u'], lv['in_u'], lv['eps_u'],
+                     drop=bool(lv['drop']))
+            d.wshape = (hs, wsz, d.X, 0, d.ypad, 0)
+            u.wshape = (hs, wsz, d.X, u.X - d.X, u.ypad, 0)        # plain operands: the skip and the level below
+            if i == 0 and self.edge_path:
+                d.route = u.route = THIN
+            lv.update(d=d, u=u, hs=hs, ws=wsz, cd_in=d.Y, cd_out=d.X, cu_in=u.X, cu_out=u.Y)
+
+    def _query_plans(self, B):
+        """Partial-row counts of every GEMM, the class of every weight gradient, and the workspace all of them need."""
+        T, n = self.dtype, self.n
+        ws_bytes = 16
+        batching = T == torch.bfloat16 and not os.environ.get('ADN_NO_WGRAD_BATCH')
+        batching_patch = batching and not os.environ.get('ADN_NO_PATCH_BATCH')
+        for i, lv in enumerate(self.levels):
+            d, u = lv['d'], lv['u']
+            hs, wsz = d.hs, d.ws
+            c_up = [d.X, u.X - d.X] if u.X - d.X else [d.X]
+            if d.route == THIN:
+                u.Pg = K.d0_dgrad_num_partials(B, hs, wsz)
+                need = [K.thin_wgrad_workspace_bytes(B, hs, wsz, 2, 64, 0), K.thin_wgrad_workspace_bytes(B, hs, wsz, 1, 64, 64)]
+            else:
+                epi_d = EPI_RAW if self._vae_level(i) else (EPI_Z_STATS if d.norm == 'batch' else EPI_ACT)
+                d.P, w1 = K.igemm_query(T, GEMM_S2, B, hs, wsz, d.ypad, 0, d.X, [d.X], epi=epi_d)               # Li fwd
+                u.Pg, w3 = K.igemm_query(T, GEMM_S2, B, hs, wsz, u.ypad, 0, u.X, c_up, epi=EPI_BWD)            # Di dgrad
+                need = [w1, w3] + [K.wgrad_workspace_bytes(T, B, *s.wshape, s.c_valid) for s in (d, u)]
+            if i == 0 and self.n1_path:
+                need.append(K.convt_n1_workspace_bytes(B, hs, wsz))                                           # D0 fwd
+            else:
+                epi_u = EPI_Z_STATS if u.norm == 'batch' else (EPI_FINAL if i == 0 else EPI_ACT)
+                u.P, w2 = K.igemm_query(T, GEMM_T2, B, hs, wsz, d.X, u.X - d.X, u.Y, [u.Y], epi=epi_u)         # Di fwd
+                need.append(w2)
+            if i > 0:
+                d.Pg, w4 = K.igemm_query(T, GEMM_T2, B, hs, wsz, d.X, 0, d.Y, [d.Y], epi=EPI_BWD)              # Li dgrad
+                need.append(w4)
+            for s in (d, u):
+                # instance-norm statistics and the bias gradients (channel sums of dz) share the workspace
+                if s.norm == 'instance':
+                    need.append(K.inorm_workspace_bytes(B, s.px, s.C))
+                if s.conv.bias is not None and not (s.tag == 'u' and i == 0):
+                    need.append(K.channel_sum_workspace_bytes(B * s.px, s.C))
+                if s.route == THIN or s.ypad != s.Y:
+                    continue
+                # patch-staged levels: candidates for the shared-split launch (_group_patch_launches); small-image
+                # levels: class of the problem in the multi-problem launch (0 = own launch) and its norm partials
+                s.patch_ok = batching_patch and K.wgrad_patch_batch_workspace_bytes(T, B, [s.wshape]) >= 0
+                if batching:
+                    s.wclass, s.wq = K.wgrad_batchable(T, B, *s.wshape)
+                    if s.wclass:
+                        s.route = MULTI
+            ws_bytes = max(ws_bytes, *need)
+        return ws_bytes
+
+    def _alloc_activations(self, B, H, W, dev):
+        """Level by level: activations, packed S2 operands, norm statistics (the order the buffers have always had)."""
+        T, n = self.dtype, self.n
+        self.x_nhwc = None if self.edge_path else torch.empty(B, H, W, self.cin_pad, dtype=T, device=dev)
+        for i, lv in enumerate(self.levels):
+            d, u = lv['d'], lv['u']
+            act = lambda c, k=1: torch.empty(B, k * d.hs, k * d.ws, c, dtype=T, device=dev)
+            lv['ad'] = act(d.C) if i < n - 1 else None
+            lv['rd'] = None if self._no_skip(i) or (i == 0 and self.skip0_leaky) else act(d.C)
             # the skip operand as its readers get it (level 0 with skip0_leaky: before the ReLU, see _skip_relu)
             lv['skip'] = lv['ad'] if i == 0 and self.skip0_leaky else lv['rd']
-            lv['Gd'] = act(cd_out)
-            lv['zd'] = act(cd_out) if lv['bn_d'] is not None or lv['in_d'] else None
-            big = lambda c, h=hs, w_=wsz: torch.empty(B, 2 * h, 2 * w_, c, dtype=T, device=dev)
+            lv['Gd'] = act(d.C)
+            lv['zd'] = d.z = act(d.C) if d.norm != 'none' else None
             if i > 0:
-                lv['zu'] = big(cu_out) if lv['bn_u'] is not None or lv['in_u'] else None
-                lv['ru'] = big(cu_out)
-                lv['keep_u'] = torch.ones(B, 2 * hs, 2 * wsz, cu_out, dtype=torch.uint8, device=dev) if lv['drop'] else None
-                lv['Gu'] = big(cu_out)
+                lv['zu'] = u.z = act(u.C, 2) if u.norm != 'none' else None
+                lv['ru'] = act(u.C, 2)
+                lv['keep_u'] = torch.ones(B, 2 * d.hs, 2 * d.ws, u.C, dtype=torch.uint8, device=dev) if u.drop else None
+                lv['Gu'] = act(u.C, 2)
             else:
-                lv['out'] = torch.empty(B, 2 * hs, 2 * wsz, cu_out, **f32)
-                lv['dz0'] = torch.empty(B, 1, 2 * hs, 2 * wsz, **f32) if self.edge_path else big(cu_out_p)
+                lv['out'] = torch.empty(B, 2 * d.hs, 2 * d.ws, u.C, dtype=torch.float32, device=dev)
+                lv['dz0'] = torch.empty(B, 1, 2 * d.hs, 2 * d.ws, dtype=torch.float32, device=dev) if self.edge_path \
+                    else act(u.ypad, 2)
             # packed weights: S2 = view of the bf16 parameter mirror (unpadded bf16 layers), own buffer when
-            # padded, the f32 master itself on the exact path; T2 = slices of one flat buffer (below)
-            for wk, X, Y, Yp in (('down', cd_out, cd_in, cd_in_p), ('up', cu_in, cu_out, cu_out_p)):
-                if Yp != Y:
-                    lv[wk + '_s2'] = torch.empty(X, 16, Yp, dtype=T, device=dev)
-                elif T != torch.float32:
-                    lv[wk + '_s2'] = self._flat_slice(self.flat_w16, lv[wk].weight).view(X, 16, Y)
-            # GEMM plans: partial rows + workspace
-            c_up0 = cd_out
-            c_up1 = cu_in - cd_out
-            edge0 = i == 0 and self.edge_path
-            epi_d = EPI_RAW if self._vae_level(i) else (EPI_Z_STATS if lv['bn_d'] is not None else EPI_ACT)
-            pd, w1 = (0, 0) if edge0 else K.igemm_query(T, GEMM_S2, B, hs, wsz, cd_in_p, 0, cd_out, [cd_out],   # Li fwd
-                                                       epi=epi_d)
-            if i == 0 and self.n1_path:
-                pu, w2 = 0, K.convt_n1_workspace_bytes(B, hs, wsz)                                  # D0 fwd
-            else:
-                pu, w2 = K.igemm_query(T, GEMM_T2, B, hs, wsz, c_up0, c_up1, cu_out, [cu_out],     # Di fwd
-                                        epi=EPI_Z_STATS if lv['bn_u'] is not None else (EPI_FINAL if i == 0 else EPI_ACT))
-            pgu, w3 = (0, 0) if edge0 else K.igemm_query(T, GEMM_S2, B, hs, wsz, cu_out_p, 0, cu_in,   # Di dgrad
-                                                         [c_up0, c_up1] if c_up1 else [c_up0], epi=EPI_BWD)
-            pgd, w4 = (0, 0) if i == 0 else K.igemm_query(T, GEMM_T2, B, hs, wsz, cd_out, 0, cd_in, [cd_in], epi=EPI_BWD)  # Li dgrad
-            w5 = 0 if edge0 else K.wgrad_workspace_bytes(T, B, hs, wsz, cd_out, 0, cd_in_p, 0,
-                                                         cd_in if cd_in_p != cd_in else 0)
-            w6 = 0 if edge0 else K.wgrad_workspace_bytes(T, B, hs, wsz, c_up0, c_up1, cu_out_p, 0,
-                                                         cu_out if cu_out_p != cu_out else 0)
-            if i == 0 and self.edge_path:
-                pgu = K.d0_dgrad_num_partials(B, hs, wsz)
-                w3 = 0
-                w5 = K.thin_wgrad_workspace_bytes(B, hs, wsz, 2, 64, 0)
-                w6 = K.thin_wgrad_workspace_bytes(B, hs, wsz, 1, 64, 64)
-            ws_bytes = max(ws_bytes, w1, w2, w3, w4, w5, w6)
-            # instance-norm statistics and the bias gradients (channel sums of dz) share the workspace
-            for tag, C, px in (('d', cd_out, hs * wsz), ('u', cu_out, 4 * hs * wsz)):
-                if lv['in_' + tag]:
-                    ws_bytes = max(ws_bytes, K.inorm_workspace_bytes(B, px, C))
-                    lv[f'mean_{tag}'] = torch.empty(B * C, **f32)
-                    lv[f'istd_{tag}'] = torch.empty(B * C, **f32)
-                if lv['down' if tag == 'd' else 'up'].bias is not None and not (tag == 'u' and i == 0):
-                    ws_bytes = max(ws_bytes, K.channel_sum_workspace_bytes(B * px, C))
-            lv.update(P_d=pd, P_u=pu, P_gu=pgu, P_gd=pgd)
-            # small-image levels: their weight gradients ride in one multi-problem launch (adn_wgrad_multi)
-            # patch-staged levels: candidates for the shared-split launch (see _patch_groups below)
-            if batching_patch and not edge0:
-                if cd_in_p == cd_in and K.wgrad_patch_batch_workspace_bytes(T, B, [(hs, wsz, cd_out, 0, cd_in_p, 0)]) >= 0:
-                    pshape_d[i] = (hs, wsz, cd_out, 0, cd_in_p, 0)
-                if cu_out_p == cu_out and K.wgrad_patch_batch_workspace_bytes(T, B, [(hs, wsz, c_up0, c_up1, cu_out_p, 0)]) >= 0:
-                    pshape_u[i] = (hs, wsz, c_up0, c_up1, cu_out_p, 0)
-            # (class of the problem -- 0 = own launch, else it rides in the multi-problem launch -- and its norm partials)
-            batching = T == torch.bfloat16 and not os.environ.get('ADN_NO_WGRAD_BATCH')
-            lv['wb_d'], lv['wbq_d'] = (K.wgrad_batchable(T, B, hs, wsz, cd_out, 0, cd_in_p, 0)
-                                       if batching and not edge0 and cd_in_p == cd_in else (0, 0))
-            lv['wb_u'], lv['wbq_u'] = (K.wgrad_batchable(T, B, hs, wsz, c_up0, c_up1, cu_out_p, 0)
-                                       if batching and not edge0 and cu_out_p == cu_out else (0, 0))
-            for tag, bn, C in (('d', lv['bn_d'], cd_out), ('u', lv['bn_u'], cu_out)):
-                if bn is None:
-                    continue
-                for nm in ('mean', 'istd', 'scale', 'shift'):
-                    lv[f'{nm}_{tag}'] = torch.empty(C, **f32)
-                lv[f'coef_{tag}'] = torch.empty(2 * C, **f32)
-                lv[f'part_{tag}'] = torch.empty((pd if tag == 'd' else pu) * 2 * C, **f32)
-        # backward stats partials: the tensor BN'd at (level i, tag) receives its final gradient from
-        #   tag 'u' (zu[i], i>=1): dgrad of D(i-1)  -> P_gu of level i-1
-        #   tag 'd' (zd[i], 1<=i<=n-2): dgrad of L(i+1) -> P_gd of level i+1
-        for i, lv in enumerate(self.levels):
-            if lv['bn_u'] is not None:
-                lv['bpart_u'] = torch.empty(self.levels[i - 1]['P_gu'] * 2 * lv['cu_out'], **f32)
-            if lv['bn_d'] is not None:
-                lv['bpart_d'] = torch.empty(self.levels[i + 1]['P_gd'] * 2 * lv['cd_out'], **f32)
-        # one flat T2 buffer + the layer table of adn_pack_t2_multi
+            # padded, the f32 master itself on the exact path; T2 = slices of one flat buffer (_build_t2)
+            for s in (d, u):
+                if s.ypad != s.Y:
+                    s.s2 = torch.empty(s.X, 16, s.ypad, dtype=T, device=dev)
+                else:                                              # (f32: channels_last memory == S2 operand)
+                    s.s2 = self._flat_slice(self.flat_p if T == torch.float32 else self.flat_w16, s.conv.weight).view(s.X, 16, s.Y)
+            self._alloc_stats(lv, B, dev)
+        self._alloc_bparts(dev)
+
+    def _alloc_stats(self, lv, B, dev):
+        """Norm statistics of one level's two sides (the backward partials: _alloc_bparts)."""
+        f32 = dict(dtype=torch.float32, device=dev)
+        for s in (lv['d'], lv['u']):
+            if s.norm == 'instance':
+                s.mean, s.istd = torch.empty(B * s.C, **f32), torch.empty(B * s.C, **f32)
+            elif s.norm == 'batch':
+                s.mean, s.istd, s.scale, s.shift = (torch.empty(s.C, **f32) for _ in range(4))
+                s.coef = torch.empty(2 * s.C, **f32)
+                s.part = torch.empty(s.P * 2 * s.C, **f32)
+
+    def _alloc_bparts(self, dev):
+        """The backward partials of the tensor normed at (level i, side) come with its final gradient: 'u' (zu[i], i >= 1)
+        from the dgrad of D(i-1), 'd' (zd[i], 1 <= i <= n-2) from the dgrad of L(i+1)."""
+        L = self.levels
+        for i, lv in enumerate(L):
+            for s in (lv['u'], lv['d']):
+                if s.norm == 'batch':
+                    s.Pb = L[i + 1]['d'].Pg if s.tag == 'd' else L[i - 1]['u'].Pg
+                    s.bpart = torch.empty(s.Pb * 2 * s.C, dtype=torch.float32, device=dev)
+
+    def _build_t2(self, dev):
+        """One flat T2 buffer + the layer table of adn_pack_t2_multi."""
         rows, t2_off, blk = [], 0, 0
-        for lv in self.levels:
-            for wk in ('down', 'up'):
-                w = lv[wk].weight
-                X, Y = w.shape[0], w.shape[1]
-                rows.append([self.offset[id(w)], X, Y, t2_off, blk])
-                lv[wk + '_t2_off'] = t2_off
-                t2_off += 16 * X * Y
-                blk += ((X + 63) // 64) * ((Y + 63) // 64) * 16
-        self.t2_all = torch.empty(t2_off, dtype=T, device=dev)
-        for lv in self.levels:
-            for wk in ('down', 'up'):
-                w = lv[wk].weight
-                o = lv[wk + '_t2_off']
-                lv[wk + '_t2'] = self.t2_all[o:o + 16 * w.shape[0] * w.shape[1]]
-        # The patch-staged weight gradients of consecutive wide levels share ONE launch with 1/n of the pixel splits each
-        # (adn_wgrad_patch_batch: n layers then write and re-read 1/n of the f32 slabs each): the down group L3, L2, L1 goes
-        # out when L1's output gradient is final, the up group D1, D2, D3 when D3's is.
-        def group(shapes):
-            idx = sorted(shapes)[:4]
-            ok = len(idx) >= 2 and idx == list(range(idx[0], idx[0] + len(idx)))
-            return idx if ok else []
-        self.pb_d, self.pb_u = group(pshape_d), group(pshape_u)
-        self.pshape = {('d', i): pshape_d[i] for i in self.pb_d}
-        self.pshape.update({('u', i): pshape_u[i] for i in self.pb_u})
-        for tag, idx in (('d', self.pb_d), ('u', self.pb_u)):
-            if idx:
-                ws_bytes = max(ws_bytes, K.wgrad_patch_batch_workspace_bytes(T, B, [self.pshape[(tag, i)] for i in idx]))
-        self._prepare_fused_norm(B, dev)
-        if self.vae is not None:
-            self._prepare_vae(B, dev)
+        for s in self._sides():
+            rows.append([self.offset[id(s.conv.weight)], s.X, s.Y, t2_off, blk])
+            s.t2_off = t2_off
+            t2_off += 16 * s.X * s.Y
+            blk += ((s.X + 63) // 64) * ((s.Y + 63) // 64) * 16
+        self.t2_all = torch.empty(t2_off, dtype=self.dtype, device=dev)
+        for s in self._sides():
+            s.t2 = self.t2_all[s.t2_off:s.t2_off + 16 * s.X * s.Y]
         self.t2_table = torch.tensor(rows, dtype=torch.int64, device=dev)
         self.t2_layers, self.t2_blocks = len(rows), blk
-        self.workspace = torch.empty(ws_bytes // 4 + 4, **f32)
-        self.red_ws = torch.empty(4096, dtype=torch.float64, device=dev)
-        self.weights_dirty = True
-        self._shape_key = key
-        self.B = B
+
+    def _group_patch_launches(self, B):
+        """The patch-staged weight gradients of consecutive wide levels share ONE launch with 1/n of the pixel splits each
+        (adn_wgrad_patch_batch: n layers then write and re-read 1/n of the f32 slabs each): the down group L3, L2, L1 goes
+        out when L1's output gradient is final, the up group D1, D2, D3 when D3's is.  Returns the slab scratch bytes."""
+        ws_bytes = 0
+        for tag in ('d', 'u'):
+            idx = [i for i, lv in enumerate(self.levels) if lv[tag].patch_ok][:4]
+            if len(idx) < 2 or idx != list(range(idx[0], idx[0] + len(idx))):
+                continue
+            group = [self.levels[i][tag] for i in idx]
+            for s in group:
+                s.route = GROUP
+            group[0 if tag == 'd' else -1].trigger = True          # the member the backward walk reaches last
+            ws_bytes = max(ws_bytes, K.wgrad_patch_batch_workspace_bytes(self.dtype, B, [s.wshape for s in group]))
+        return ws_bytes
 
     # ------------------------------------------------------------------ topology hooks (cVAE: CVAEEngine)
     def _buffer_key(self, x):
@@ -331,27 +380,13 @@ class UNetEngine(FlatParamEngine):
         """clip_grad_norm_ (train.py:689) without a pass over the 54 M-element gradient: the kernel that writes a
         conv layer's final dW leaves partial sums of dW^2 in ``sq_all`` (AdnWgradDesc.sq_partials); the parameters
         without such a kernel (BatchNorm affine, bias, the thin edge layers) are covered by ``norm_ranges``."""
-        T = self.dtype
         self.sq_all = self.norm_ranges = None
         if os.environ.get('ADN_NO_FUSED_NORM'):
             return
-        counts, covered = [], set()
-        for i, lv in enumerate(self.levels):
-            edge0 = i == 0 and self.edge_path
-            hs, wsz = lv['hs'], lv['ws']
-            c_up0, c_up1 = lv['cd_out'], lv['cu_in'] - lv['cd_out']
-            nd = 0 if edge0 else K.wgrad_sq_count(T, B, hs, wsz, lv['cd_out'], 0, lv['down_ypad'], 0,
-                                                  lv['cd_in'] if lv['down_ypad'] != lv['cd_in'] else 0)
-            nu = 0 if edge0 else K.wgrad_sq_count(T, B, hs, wsz, c_up0, c_up1, lv['up_ypad'], 0,
-                                                  lv['cu_out'] if lv['up_ypad'] != lv['cu_out'] else 0)
-            if lv['wb_d']:                   # a problem of the multi-problem launch runs unsplit: its own partial count
-                nd = lv['wbq_d']
-            if lv['wb_u']:
-                nu = lv['wbq_u']
-            for wk, cnt in (('down', nd), ('up', nu)):
-                counts.append((lv, wk, cnt))
-                if cnt:
-                    covered.add(id(lv[wk].weight))
+        # (a problem of the multi-problem launch runs unsplit: its own partial count)
+        counts = [0 if s.route == THIN else s.wq if s.wclass else K.wgrad_sq_count(self.dtype, B, *s.wshape, s.c_valid)
+                  for s in self._sides()]
+        covered = {id(s.conv.weight) for s, cnt in zip(self._sides(), counts) if cnt}
         rows = []
         for p, off, numel in self.param_meta:
             if id(p) in covered:
@@ -360,136 +395,208 @@ class UNetEngine(FlatParamEngine):
                 rows.append([off + o, (min(self.NORM_ROW, numel - o) + 3) // 4 * 4])   # the tail reads zero padding
         if not covered or len(rows) > 1024:
             return
-        self.sq_all = torch.zeros(sum(c for _, _, c in counts), dtype=torch.float64, device=dev)
+        self.sq_all = torch.zeros(sum(counts), dtype=torch.float64, device=dev)
         o = 0
-        for lv, wk, cnt in counts:
-            lv[wk + '_sq'] = self.sq_all[o:o + cnt] if cnt else None
+        for s, cnt in zip(self._sides(), counts):
+            s.sq = self.sq_all[o:o + cnt] if cnt else None
             o += cnt
         self.norm_ranges = torch.tensor(rows, dtype=torch.int64, device=dev).view(-1, 2) if rows else None
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x, training):
-        if not x.is_cuda:
-            raise RuntimeError('UnetGenerator.forward needs a HIP device tensor (libadn has no CPU path)')
-        x = x.contiguous().float()
+    def _begin(self, x):
+        """Buffers, packed weights and the input operand of a forward walk over ``x`` (contiguous f32 NCHW)."""
         self._prepare(x)
         if self.weights_dirty or self._packed_version != self._version_sum():
             self._pack_weights()
-        T, B, n, L, ws = self.dtype, self.B, self.n, self.levels, self.workspace
         if self.edge_path:
             self._x_in, self._x_ver = x, x._version          # the first conv and its weight gradient read x itself
         else:
             K.nchw_to_nhwc(x, self.x_nhwc)
+
+    def forward(self, x, training):
+        if not x.is_cuda:
+            raise RuntimeError('UnetGenerator.forward needs a HIP device tensor (libadn has no CPU path)')
+        x = x.contiguous().float()
+        self._begin(x)
         self._drop_active = bool(training) and self.uses_dropout
         if self._drop_active:
             self._draw_masks()
-        # ---- down path
-        for i, lv in enumerate(L):
-            src = self.x_nhwc if i == 0 else L[i - 1]['ad']
-            C, hs, wsz = lv['cd_out'], lv['hs'], lv['ws']
-            bn = lv['bn_d']
-            if self._vae_level(i):
-                K.igemm(T, GEMM_S2, B, hs, wsz, src, None, lv['down_s2'], C, EPI_RAW, [K.Seg(C, out0=self.vae_h)], ws)
-                self._vae_forward(training)
-            elif i == 0 and self.edge_path:
-                K.l0_forward(x, self._flat_slice(self.flat_p, lv['down'].weight), B, hs, wsz, LEAKY, lv['ad'], lv['rd'])
-            elif lv['in_d']:              # raw z (+ bias) through the identity form of the ACT epilogue, then the norm
-                K.igemm(T, GEMM_S2, B, hs, wsz, src, None, lv['down_s2'], C, EPI_ACT,
-                        [K.Seg(C, out0=lv['zd'], bias=lv['down'].bias, slope=1.0)], ws, algo_c=lv['cd_in'])
-                K.inorm_fwd(lv['zd'], B, hs * wsz, C, lv['eps_d'], LEAKY, lv['mean_d'], lv['istd_d'], lv['ad'], lv['rd'], ws)
-            elif bn is None:
-                K.igemm(T, GEMM_S2, B, hs, wsz, src, None, lv['down_s2'], C, EPI_ACT,
-                        [K.Seg(C, out0=lv['ad'], out1=lv['rd'], bias=lv['down'].bias, slope=LEAKY)], ws,
-                        algo_c=lv['cd_in'])
-            elif training:
-                K.igemm(T, GEMM_S2, B, hs, wsz, src, None, lv['down_s2'], C, EPI_Z_STATS,
-                        [K.Seg(C, out0=lv['zd'], partials=lv['part_d'])], ws)
-                self._bn_forward(lv, 'd', bn, B * hs * wsz, lv['P_d'], lv['zd'], LEAKY, lv['ad'], lv['rd'])
-            else:
-                K.bn_eval_affine(bn.weight, bn.bias, bn.running_mean, bn.running_var, BN_EPS, lv['scale_d'],
-                                 lv['shift_d'])
-                K.igemm(T, GEMM_S2, B, hs, wsz, src, None, lv['down_s2'], C, EPI_ACT,
-                        [K.Seg(C, out0=lv['ad'], out1=lv['rd'], scale=lv['scale_d'], shift=lv['shift_d'],
-                               slope=LEAKY)], ws)
-        # ---- up path
-        for i in reversed(range(n)):
-            lv = L[i]
-            in0, in1 = self._up_inputs(i)
-            C, hs, wsz = lv['cu_out'], lv['hs'], lv['ws']
-            bn = lv['bn_u']
-            if i == 0:
-                bias = lv['up'].bias
-                fa = self.final_act
-                if self.n1_path:
-                    K.convt_n1_forward(T, B, hs, wsz, in0, in1, self._flat_slice(self.flat_p, lv['up'].weight), bias,
-                                       fa, lv['out'], ws, relu_in0=self._skip_relu(i))
-                else:
-                    K.igemm(T, GEMM_T2, B, hs, wsz, in0, in1, lv['up_t2'], C, EPI_FINAL,
-                            [K.Seg(C, out0=lv['out'], bias=bias, final_act=fa)], ws)
-            elif lv['in_u']:
-                keep = lv['keep_u'] if self._drop_active else None
-                K.igemm(T, GEMM_T2, B, hs, wsz, in0, in1, lv['up_t2'], C, EPI_ACT,
-                        [K.Seg(C, out0=lv['zu'], bias=lv['up'].bias, slope=1.0)], ws)
-                K.inorm_fwd(lv['zu'], B, 4 * hs * wsz, C, lv['eps_u'], 0.0, lv['mean_u'], lv['istd_u'], None, lv['ru'], ws,
-                            keep=keep, keep_scale=1.0 / (1.0 - self.DROP_P))
-            elif bn is None:
-                K.igemm(T, GEMM_T2, B, hs, wsz, in0, in1, lv['up_t2'], C, EPI_ACT, [K.Seg(C, out1=lv['ru'])], ws)
-                if lv['drop'] and self._drop_active:
-                    K.dropout_apply(lv['ru'], lv['keep_u'], 1.0 / (1.0 - self.DROP_P))
-            elif training:
-                K.igemm(T, GEMM_T2, B, hs, wsz, in0, in1, lv['up_t2'], C, EPI_Z_STATS,
-                        [K.Seg(C, out0=lv['zu'], partials=lv['part_u'])], ws)
-                self._bn_forward(lv, 'u', bn, B * 4 * hs * wsz, lv['P_u'], lv['zu'], 0.0, None, lv['ru'])
-                if lv['drop']:            # (dropout levels are <= 8 x 8 images: an unfused pass over ru)
-                    K.dropout_apply(lv['ru'], lv['keep_u'], 1.0 / (1.0 - self.DROP_P))
-            else:
-                K.bn_eval_affine(bn.weight, bn.bias, bn.running_mean, bn.running_var, BN_EPS, lv['scale_u'],
-                                 lv['shift_u'])
-                K.igemm(T, GEMM_T2, B, hs, wsz, in0, in1, lv['up_t2'], C, EPI_ACT,
-                        [K.Seg(C, out1=lv['ru'], scale=lv['scale_u'], shift=lv['shift_u'])], ws)
-        out = L[0]['out']                                   # [B, H, W, Cout] f32
-        Cout = L[0]['cu_out']
+        for i in range(self.n):
+            self._down_conv(i, x, training)
+        if self.vae is not None:
+            self._vae_forward(training)
+        out = self.levels[0]['out']                         # [B, H, W, Cout] f32
+        for i in reversed(range(self.n)):
+            self._up_conv(i, *self._up_inputs(i), out, training)
+        return self._nchw(out)
+
+    def _nchw(self, out):
+        """f32 [N, H, W, C] -> [N, C, H, W]: a view for one channel."""
+        N, H, W, Cout = out.shape
         if Cout == 1:
-            return out.view(B, 1, out.shape[1], out.shape[2])
-        res = torch.empty(B, Cout, out.shape[1], out.shape[2], dtype=torch.float32, device=out.device)
+            return out.view(N, 1, H, W)
+        res = torch.empty(N, Cout, H, W, dtype=torch.float32, device=out.device)
         K.nhwc_to_nchw(out, res)
         return res
+
+    def _eval_affine(self, s):
+        """Eval-mode BatchNorm of a side as the scale / shift its GEMM epilogue applies."""
+        bn = s.bn
+        K.bn_eval_affine(bn.weight, bn.bias, bn.running_mean, bn.running_var, BN_EPS, s.scale, s.shift)
+
+    def _down_conv(self, i, x, training):
+        """Strided conv of level i with its norm: writes ad[i] (LeakyReLU, the next level's operand) and rd[i] (ReLU, the
+        skip operand).  The VAE level writes the raw f32 ``vae_h`` only: the bottleneck is the caller's next call."""
+        T, B, ws, lv = self.dtype, self.B, self.workspace, self.levels[i]
+        s, C, ad, rd = lv['d'], lv['d'].C, lv['ad'], lv['rd']
+
+        def gemm(epi, **seg):
+            K.igemm(T, GEMM_S2, B, s.hs, s.ws, self.x_nhwc if i == 0 else self.levels[i - 1]['ad'], None, s.s2, C, epi,
+                    [K.Seg(C, **seg)], ws, algo_c=s.Y)
+        if self._vae_level(i):
+            gemm(EPI_RAW, out0=self.vae_h)
+        elif s.route == THIN:
+            K.l0_forward(x, self._flat_slice(self.flat_p, s.conv.weight), B, s.hs, s.ws, LEAKY, ad, rd)
+        elif s.norm == 'instance':        # raw z (+ bias) through the identity form of the ACT epilogue, then the norm
+            gemm(EPI_ACT, out0=s.z, bias=s.conv.bias, slope=1.0)
+            K.inorm_fwd(s.z, B, s.px, C, s.eps, LEAKY, s.mean, s.istd, ad, rd, ws)
+        elif s.norm == 'none':
+            gemm(EPI_ACT, out0=ad, out1=rd, bias=s.conv.bias, slope=LEAKY)
+        elif training:
+            gemm(EPI_Z_STATS, out0=s.z, partials=s.part)
+            self._bn_forward(s, LEAKY, ad, rd)
+        else:
+            self._eval_affine(s)
+            gemm(EPI_ACT, out0=ad, out1=rd, scale=s.scale, shift=s.shift, slope=LEAKY)
+
+    def _up_conv(self, i, in0, in1, out, training, affine=True):
+        """Transposed conv of level i over the virtual concat (in0, in1) with its norm, ReLU and dropout: writes ru[i], or
+        for level 0 the head into ``out`` (f32 [B, H, W, Cout]).  ``affine=False``: the caller has issued _eval_affine."""
+        T, B, ws, lv = self.dtype, self.B, self.workspace, self.levels[i]
+        s, C, ru = lv['u'], lv['u'].C, lv.get('ru')
+        keep = lv.get('keep_u') if s.drop and training else None
+        keep_scale = 1.0 / (1.0 - self.DROP_P)
+
+        def gemm(epi, **seg):
+            K.igemm(T, GEMM_T2, B, s.hs, s.ws, in0, in1, s.t2, C, epi, [K.Seg(C, **seg)], ws)
+        if i == 0 and self.n1_path:
+            K.convt_n1_forward(T, B, s.hs, s.ws, in0, in1, self._flat_slice(self.flat_p, s.conv.weight), s.conv.bias,
+                               self.final_act, out, ws, relu_in0=self._skip_relu(i))
+        elif i == 0:
+            gemm(EPI_FINAL, out0=out, bias=s.conv.bias, final_act=self.final_act)
+        elif s.norm == 'instance':
+            gemm(EPI_ACT, out0=s.z, bias=s.conv.bias, slope=1.0)
+            K.inorm_fwd(s.z, B, s.px, C, s.eps, 0.0, s.mean, s.istd, None, ru, ws, keep=keep, keep_scale=keep_scale)
+        elif s.norm == 'none':
+            gemm(EPI_ACT, out1=ru)
+        elif training:
+            gemm(EPI_Z_STATS, out0=s.z, partials=s.part)
+            self._bn_forward(s, 0.0, None, ru)
+        else:
+            if affine:
+                self._eval_affine(s)
+            gemm(EPI_ACT, out1=ru, scale=s.scale, shift=s.shift)
+        if keep is not None and s.norm != 'instance':     # (dropout levels are <= 8 x 8 images: an unfused pass over ru)
+            K.dropout_apply(ru, keep, keep_scale)
 
     # tensors up to this many elements take the one-launch finalize + apply kernels (innermost levels: the two
     # separate launches cost 6-9 us each there, launch-latency bound)
     BN_FUSED_MAX = int(os.environ.get('ADN_BN_FUSED_MAX', 1 << 20))
 
-    def _bn_forward(self, lv, tag, bn, count, P, z, slope, out_leaky, out_relu):
-        """Train-mode BatchNorm + activation of a raw conv output: statistics finalize (+ running stats) and apply."""
+    def _bn_one_launch(self, s):
+        return self.B * s.px * s.C <= self.BN_FUSED_MAX and s.C % 32 == 0
+
+    def _bn_forward(self, s, slope, out_leaky, out_relu):
+        """Train-mode BatchNorm + activation of a side's raw conv output: statistics finalize (+ running stats), apply."""
+        bn, count = s.bn, self.B * s.px
         track = bn.track_running_stats and bn.running_mean is not None
-        C = lv[f'mean_{tag}'].numel()
-        args = (lv[f'part_{tag}'], P, C, count, bn.weight, bn.bias, BN_EPS,
+        args = (s.part, s.P, s.C, count, bn.weight, bn.bias, BN_EPS,
                 BN_MOMENTUM if bn.momentum is None else bn.momentum,
                 bn.running_mean if track else None, bn.running_var if track else None,
-                bn.num_batches_tracked if track else None,
-                lv[f'mean_{tag}'], lv[f'istd_{tag}'], lv[f'scale_{tag}'], lv[f'shift_{tag}'])
-        if count * C <= self.BN_FUSED_MAX and C % 32 == 0:
-            K.bn_fwd_fused(*args, z, count, slope, out_leaky, out_relu)
+                bn.num_batches_tracked if track else None, s.mean, s.istd, s.scale, s.shift)
+        if self._bn_one_launch(s):
+            K.bn_fwd_fused(*args, s.z, count, slope, out_leaky, out_relu)
         else:
             K.bn_fwd_finalize(*args)
-            K.bn_act(z, count, C, lv[f'scale_{tag}'], lv[f'shift_{tag}'], slope, out_leaky, out_relu)
-
-    def _bn_backward(self, lv, tag, bn, count, P, g, z):
-        """BatchNorm backward of the tensor BN'd at (level, tag): dgamma / dbeta + dz in place of g."""
-        C = lv[f'mean_{tag}'].numel()
-        dg, db = self._flat_slice(self.flat_g, bn.weight), self._flat_slice(self.flat_g, bn.bias)
-        if count * C <= self.BN_FUSED_MAX and C % 32 == 0:
-            K.bn_bwd_fused(lv[f'bpart_{tag}'], P, C, count, dg, db, g, z, count, lv[f'scale_{tag}'], lv[f'mean_{tag}'],
-                           lv[f'istd_{tag}'])
-        else:
-            K.bn_bwd_finalize(lv[f'bpart_{tag}'], P, C, count, dg, db, lv[f'coef_{tag}'])
-            K.bn_bwd_apply(g, z, count, C, lv[f'scale_{tag}'], lv[f'mean_{tag}'], lv[f'istd_{tag}'], lv[f'coef_{tag}'])
+            K.bn_act(s.z, count, s.C, s.scale, s.shift, slope, out_leaky, out_relu)
 
     # ------------------------------------------------------------------ backward
+    def _norm_backward(self, s, g):
+        """d loss / d (activation input) ``g`` of a side -> d loss / d (conv output), in place: the norm's backward (BatchNorm:
+        + dgamma / dbeta), the dropout factor 1 / (1 - p) of a dropout level, and the conv's bias gradient.  Returns g."""
+        B, ws = self.B, self.workspace
+        gscale = 1.0 / (1.0 - self.DROP_P) if s.drop and self._drop_active else 1.0
+        scaled = [g]
+        if s.norm == 'instance':
+            K.inorm_bwd(g, s.z, s.mean, s.istd, B, s.px, s.C, gscale, ws)
+            scaled = []
+        elif s.norm == 'batch':
+            count = B * s.px
+            dg, db = self._flat_slice(self.flat_g, s.bn.weight), self._flat_slice(self.flat_g, s.bn.bias)
+            if self._bn_one_launch(s):
+                K.bn_bwd_fused(s.bpart, s.Pb, s.C, count, dg, db, g, s.z, count, s.scale, s.mean, s.istd)
+            else:
+                K.bn_bwd_finalize(s.bpart, s.Pb, s.C, count, dg, db, s.coef)
+                K.bn_bwd_apply(g, s.z, count, s.C, s.scale, s.mean, s.istd, s.coef)
+            scaled = [g, dg, db]                          # BatchNorm backward is linear in g: the factor rides behind it
+        if gscale != 1.0:                                 # (no norm: the masked gradient is dz)
+            for t in scaled:
+                K.dropout_apply(t, None, gscale)
+        if s.conv.bias is not None:                       # (instance: every conv has a bias)
+            K.channel_sum(g, B * s.px, s.C, s.C, self._flat_slice(self.flat_g, s.conv.bias), ws)
+        return g
+
+    def _grad_seg(self, s, g, ref, slope, accumulate=False):
+        """The segment by which a dgrad GEMM writes ``g``, the gradient of the activation behind side ``s`` (mask from
+        ``ref``), and, in front of a BatchNorm, the partial sums of its backward statistics."""
+        kw = {}
+        if s.norm == 'batch':
+            kw = dict(z=s.z, mean=s.mean, istd=s.istd, partials=s.bpart)
+            if not s.drop:    # (a dropped unit is a zero of ru: on a dropout level the mask must come from ref, never from z)
+                kw.update(scale=s.scale, shift=s.shift)
+        return K.Seg(s.C, out0=g, ref=ref, slope=slope, accumulate=accumulate, **kw)
+
     def _ready(self, param):
         if self.on_grad_ready is not None:
             off = self.offset[id(param)]
             _lib.record_py(lambda: self.on_grad_ready(off))
+
+    def _flush_wgrad(self, pend):
+        if pend[MULTI]:
+            K.wgrad_multi(self.dtype, self.B, pend[MULTI])
+            del pend[MULTI][:]
+
+    def _emit_wgrad(self, pend, s, plain0, plain1, gath, fused_norm, relu_plain0=False):
+        """Weight gradient of side ``s`` by the route _prepare chose.  Nothing inside backward reads a dW and the operands
+        stay untouched until the end of the pass, so the small-image problems are collected in ``pend[MULTI]`` (one
+        adn_wgrad_multi launch per 8) and the members of a patch-staged group in ``pend[tag]`` until its trigger.  Under
+        the reducer's gradient-ready hook every dW goes out as early as possible: the collected problems then leave as
+        one-problem launches of the same entry point -- same kernel form, unsplit --, so both modes produce identical
+        bits."""
+        T, B, ws = self.dtype, self.B, self.workspace
+        dw = self._flat_slice(self.flat_g, s.conv.weight)
+        prob = (s.hs, s.ws, plain0, plain1, gath, None, dw, s.sq if fused_norm else None)
+        ready = True
+        if s.route == THIN:
+            K.thin_wgrad(gath, plain0, plain1, B, s.hs, s.ws, dw, ws, relu_plain0=relu_plain0)
+        elif s.route == MULTI:
+            if len(pend[MULTI]) == 8:
+                self._flush_wgrad(pend)
+            pend[MULTI].append(prob)
+            if self.on_grad_ready is not None:
+                self._flush_wgrad(pend)
+        else:
+            if s.tag == 'd':                              # back at the wide levels: the collected small ones go first
+                self._flush_wgrad(pend)
+            if s.route == GROUP:
+                pend[s.tag].append(prob)
+                if s.trigger:                             # all of the group in one launch
+                    K.wgrad_patch_batch(T, B, pend[s.tag], ws)
+                ready = s.trigger
+            else:
+                K.wgrad(T, B, *prob[:6], dw, ws, c_valid=s.c_valid, sq=prob[7])
+        if ready:
+            self._ready(s.conv.weight)
 
     def dz_target(self):
         """Where a loss kernel may write d loss / d pre-activation of the output directly (adn_loss_finish_dz), together
@@ -516,128 +623,39 @@ class UNetEngine(FlatParamEngine):
             K.final_act_bwd(gout, l0['out'], self.final_act, l0['dz0'])
             if up0.bias is not None:
                 K.sum_to_scalar(l0['dz0'], self._flat_slice(self.flat_g, up0.bias), self.red_ws)
+        pend = {MULTI: [], 'd': [], 'u': []}              # weight gradients waiting for their launch (_emit_wgrad)
         # ---- up layers, outermost first
-        # (weight gradients of the small-image levels are collected and launched together: nothing inside backward reads
-        #  them, and their operands stay untouched until the end of the pass)
-        batch = []                        # problems of either class (kernels.wgrad_multi)
-        held_u, held_d = [], []           # patch-staged groups (see _prepare: pb_u / pb_d)
-        # (the reducer's gradient-ready hook wants every dW as early as possible: the same problems then go out as
-        #  one-problem launches of the same entry point -- same kernel form, unsplit --, so both modes produce identical bits)
-        use_batch = self.on_grad_ready is None
-
-        def flush():
-            if batch:
-                K.wgrad_multi(T, B, batch)
-                del batch[:]
         for i in range(n):
-            lv = L[i]
-            hs, wsz = lv['hs'], lv['ws']
-            gscale = 1.0 / (1.0 - self.DROP_P) if lv['drop'] and self._drop_active else 1.0
-            if i == 0:
-                dz = lv['dz0']
-            elif lv['in_u']:
-                K.inorm_bwd(lv['Gu'], lv['zu'], lv['mean_u'], lv['istd_u'], B, 4 * hs * wsz, lv['cu_out'], gscale, ws)
-                dz = lv['Gu']
-            elif lv['bn_u'] is None:
-                dz = lv['Gu']                             # no norm: the masked gradient is dz
-                if gscale != 1.0:
-                    K.dropout_apply(dz, None, gscale)
-            else:
-                self._bn_backward(lv, 'u', lv['bn_u'], B * 4 * hs * wsz, L[i - 1]['P_gu'], lv['Gu'], lv['zu'])
-                dz = lv['Gu']
-                if gscale != 1.0:                         # BatchNorm backward is linear in g: the factor rides behind it
-                    bn = lv['bn_u']
-                    for t in (dz, self._flat_slice(self.flat_g, bn.weight), self._flat_slice(self.flat_g, bn.bias)):
-                        K.dropout_apply(t, None, gscale)
-            if i > 0 and lv['up'].bias is not None:       # (instance: every transposed conv has a bias)
-                K.channel_sum(dz, B * 4 * hs * wsz, lv['cu_out'], lv['cu_out'], self._flat_slice(self.flat_g, lv['up'].bias), ws)
+            lv, s = L[i], L[i]['u']
+            dz = lv['dz0'] if i == 0 else self._norm_backward(s, lv['Gu'])
             in0, in1 = self._up_inputs(i)
             # (ref is only compared with 0: the LeakyReLU copy of level 0 gives the same mask as the ReLU copy)
             segs = [] if self._no_skip(i) else [K.Seg(lv['cd_out'], out0=lv['Gd'], ref=lv['skip'], slope=0.0)]
             if i < n - 1:
                 nx = L[i + 1]
-                if nx['bn_u'] is None:
-                    segs.append(K.Seg(nx['cu_out'], out0=nx['Gu'], ref=nx['ru'], slope=0.0))
-                else:
-                    # (a dropped unit is a zero of ru: on a dropout level the mask must come from ref, never from z)
-                    aff = {} if nx['drop'] else dict(scale=nx['scale_u'], shift=nx['shift_u'])
-                    segs.append(K.Seg(nx['cu_out'], out0=nx['Gu'], ref=nx['ru'], slope=0.0, z=nx['zu'],
-                                      mean=nx['mean_u'], istd=nx['istd_u'], partials=nx['bpart_u'], **aff))
-            if i == 0 and self.edge_path:
-                K.thin_wgrad(dz, in0, in1, B, hs, wsz, self._flat_slice(self.flat_g, lv['up'].weight), ws,
-                             relu_plain0=self._skip_relu(i))
-                self._ready(lv['up'].weight)
-                K.d0_dgrad(dz, self._flat_slice(self.flat_p, lv['up'].weight), B, hs, wsz, segs[0], segs[1])
-                continue
-            if i in self.pb_u:
-                held_u.append((hs, wsz, in0, in1, dz, None, self._flat_slice(self.flat_g, lv['up'].weight),
-                               lv['up_sq'] if fused_norm else None))
-                if i == self.pb_u[-1]:                    # the group's last (innermost) level: all of them in one launch
-                    K.wgrad_patch_batch(T, B, held_u, ws)
-                    self._ready(lv['up'].weight)
-            elif lv['wb_u']:
-                if len(batch) == 8:
-                    flush()
-                batch.append((hs, wsz, in0, in1, dz, None, self._flat_slice(self.flat_g, lv['up'].weight),
-                              lv['up_sq'] if fused_norm else None))
-                if not use_batch:
-                    flush()
+                segs.append(self._grad_seg(nx['u'], nx['Gu'], nx['ru'], 0.0))
+            self._emit_wgrad(pend, s, in0, in1, dz, fused_norm, relu_plain0=self._skip_relu(i))
+            if s.route == THIN:
+                K.d0_dgrad(dz, self._flat_slice(self.flat_p, s.conv.weight), B, s.hs, s.ws, segs[0], segs[1])
             else:
-                K.wgrad(T, B, hs, wsz, in0, in1, dz, None, self._flat_slice(self.flat_g, lv['up'].weight), ws,
-                        c_valid=lv['cu_out'] if (i == 0 and self.cout_pad != lv['cu_out']) else 0,
-                        sq=lv['up_sq'] if fused_norm else None)
-            if i not in self.pb_u:
-                self._ready(lv['up'].weight)
-            K.igemm(T, GEMM_S2, B, hs, wsz, dz, None, lv['up_s2'], lv['cu_in'], EPI_BWD, segs, ws,
-                    algo_c=lv['cu_out'])
+                K.igemm(T, GEMM_S2, B, s.hs, s.ws, dz, None, s.s2, s.X, EPI_BWD, segs, ws, algo_c=s.Y)
         if self.vae is not None:
             self._vae_backward()                          # Gd[n-1]: d h_recon -> d h
         # ---- down layers, innermost first
         for i in reversed(range(n)):
-            lv = L[i]
-            hs, wsz = lv['hs'], lv['ws']
-            if lv['bn_d'] is not None:
-                self._bn_backward(lv, 'd', lv['bn_d'], B * hs * wsz, L[i + 1]['P_gd'], lv['Gd'], lv['zd'])
-            elif lv['in_d']:
-                K.inorm_bwd(lv['Gd'], lv['zd'], lv['mean_d'], lv['istd_d'], B, hs * wsz, lv['cd_out'], 1.0, ws)
-            if lv['down'].bias is not None:
-                K.channel_sum(lv['Gd'], B * hs * wsz, lv['cd_out'], lv['cd_out'],
-                              self._flat_slice(self.flat_g, lv['down'].bias), ws)
+            lv, s = L[i], L[i]['d']
+            g = self._norm_backward(s, lv['Gd'])
             src = self.x_nhwc if i == 0 else L[i - 1]['ad']
-            if i == 0 and self.edge_path:
+            if s.route == THIN:
                 if self._x_in._version != self._x_ver:
                     raise RuntimeError('the network input was modified in place between forward and backward')
-                K.thin_wgrad(self._x_in, lv['Gd'], None, B, hs, wsz, self._flat_slice(self.flat_g, lv['down'].weight), ws)
-            elif i in self.pb_d:
-                flush()
-                held_d.append((hs, wsz, lv['Gd'], None, src, None, self._flat_slice(self.flat_g, lv['down'].weight),
-                               lv['down_sq'] if fused_norm else None))
-                if i == self.pb_d[0]:                     # the group's last (outermost) level
-                    K.wgrad_patch_batch(T, B, held_d, ws)
-            elif lv['wb_d']:
-                if len(batch) == 8:
-                    flush()
-                batch.append((hs, wsz, lv['Gd'], None, src, None, self._flat_slice(self.flat_g, lv['down'].weight),
-                              lv['down_sq'] if fused_norm else None))
-                if not use_batch:
-                    flush()
-            else:
-                flush()                                   # back at the wide levels: the collected small ones go first
-                K.wgrad(T, B, hs, wsz, lv['Gd'], None, src, None, self._flat_slice(self.flat_g, lv['down'].weight), ws,
-                        c_valid=lv['cd_in'] if (i == 0 and self.cin_pad != lv['cd_in']) else 0,
-                        sq=lv['down_sq'] if fused_norm else None)
-            if i not in self.pb_d or i == self.pb_d[0]:
-                self._ready(lv['down'].weight)
+                src = self._x_in
+            self._emit_wgrad(pend, s, g, None, src, fused_norm)
             if i > 0:
-                pv = L[i - 1]
-                acc = not self._no_skip(i - 1)            # no skip above the cVAE bottleneck: the only writer of Gd
-                seg = K.Seg(pv['cd_out'], out0=pv['Gd'], ref=pv['ad'], slope=LEAKY, accumulate=acc)
-                if pv['bn_d'] is not None:
-                    seg = K.Seg(pv['cd_out'], out0=pv['Gd'], ref=pv['ad'], slope=LEAKY, accumulate=acc,
-                                z=pv['zd'], mean=pv['mean_d'], istd=pv['istd_d'], partials=pv['bpart_d'],
-                                scale=pv['scale_d'], shift=pv['shift_d'])
-                K.igemm(T, GEMM_T2, B, hs, wsz, lv['Gd'], None, lv['down_t2'], lv['cd_in'], EPI_BWD, [seg], ws)
-        flush()
+                pv = L[i - 1]                             # (no skip above the cVAE bottleneck: the only writer of Gd)
+                seg = self._grad_seg(pv['d'], pv['Gd'], pv['ad'], LEAKY, accumulate=not self._no_skip(i - 1))
+                K.igemm(T, GEMM_T2, B, s.hs, s.ws, g, None, s.t2, s.Y, EPI_BWD, [seg], ws)
+        self._flush_wgrad(pend)
         if self.on_grad_ready is not None:
             _lib.record_py(lambda: self.on_grad_ready(0))
 

@@ -99,19 +99,34 @@ def _igemm_desc(dtype, geom, B, Hs, Ws, in0, in1, w, N, epi, segs, workspace=Non
     return d
 
 
-def igemm_query(dtype, geom, B, Hs, Ws, C0, C1, N, seg_channels, ks=0, epi=EPI_RAW):
-    """(num stats partial rows, workspace bytes) for a shape, without touching the GPU.  ``epi``: the epilogue the launch
-    will use -- the kernel choice (and with it the number of partial rows of the Z_STATS / BWD epilogues) depends on it."""
+def _launch(label, flops, entry, *args):
+    """Call ``entry`` on the current stream, annotate the recorded launch with its label and algorithmic FLOPs, time it
+    under PROFILE."""
+    ev = _prof_begin()
+    _lib.call(entry, *args, _stream())
+    _lib.annotate(label=label, flops=flops)
+    if ev is not None:
+        _prof_end(ev, label, flops)
+
+
+def _igemm_shape_desc(dtype, geom, B, Hs, Ws, C0, C1, N, seg_channels, ks, epi):
+    """A descriptor of the shape alone for the host-only queries (dummy non-null operands: they only validate and plan)."""
     d = AdnIgemmDesc()
     d.ks = ks
     d.dtype, d.geom, d.B, d.Hs, d.Ws, d.C0, d.C1, d.N = dtype_code(dtype), geom, B, Hs, Ws, C0, C1, N
     d.in0 = d.w = 1
     d.in1 = 1 if C1 else None
     d.epi = epi
-    d.seg[0].channels = seg_channels[0]
-    d.seg[0].out0 = d.seg[0].ref = 1                    # (dummy non-null operands: the query only validates and plans)
-    d.seg[1].channels = seg_channels[1] if len(seg_channels) > 1 else 0
-    d.seg[1].out0 = d.seg[1].ref = 1
+    for i in (0, 1):
+        d.seg[i].channels = seg_channels[i] if i < len(seg_channels) else 0
+        d.seg[i].out0 = d.seg[i].ref = 1
+    return d
+
+
+def igemm_query(dtype, geom, B, Hs, Ws, C0, C1, N, seg_channels, ks=0, epi=EPI_RAW):
+    """(num stats partial rows, workspace bytes) for a shape, without touching the GPU.  ``epi``: the epilogue the launch
+    will use -- the kernel choice (and with it the number of partial rows of the Z_STATS / BWD epilogues) depends on it."""
+    d = _igemm_shape_desc(dtype, geom, B, Hs, Ws, C0, C1, N, seg_channels, ks, epi)
     lib = _lib.load()
     p = lib.adn_igemm_num_partials(C.byref(d))
     wsb = lib.adn_igemm_workspace_bytes(C.byref(d))
@@ -122,15 +137,7 @@ def igemm_query(dtype, geom, B, Hs, Ws, C0, C1, N, seg_channels, ks=0, epi=EPI_R
 
 def igemm_describe(dtype, geom, B, Hs, Ws, C0, C1, N, seg_channels, ks=0, epi=EPI_RAW):
     """The plan line of adn_igemm_describe for a shape ('ring bm=256 ...'; the first word is the kernel form), host only."""
-    d = AdnIgemmDesc()
-    d.ks = ks
-    d.dtype, d.geom, d.B, d.Hs, d.Ws, d.C0, d.C1, d.N = dtype_code(dtype), geom, B, Hs, Ws, C0, C1, N
-    d.in0 = d.w = 1
-    d.in1 = 1 if C1 else None
-    d.epi = epi
-    for i, c in enumerate(seg_channels[:2]):
-        d.seg[i].channels = c
-        d.seg[i].out0 = d.seg[i].ref = 1                # (dummy non-null operands: the query only validates and plans)
+    d = _igemm_shape_desc(dtype, geom, B, Hs, Ws, C0, C1, N, seg_channels, ks, epi)
     buf = C.create_string_buffer(256)
     lib = _lib.load()
     if lib.adn_igemm_describe(C.byref(d), buf, len(buf)) != 0:
@@ -141,14 +148,10 @@ def igemm_describe(dtype, geom, B, Hs, Ws, C0, C1, N, seg_channels, ks=0, epi=EP
 def igemm(dtype, geom, B, Hs, Ws, in0, in1, w, N, epi, segs, workspace=None, algo_c=None, ks=0):
     """algo_c: real (unpadded) gathered channel count, only used for the algorithmic FLOP count."""
     d = _igemm_desc(dtype, geom, B, Hs, Ws, in0, in1, w, N, epi, segs, workspace, ks)
-    ev = _prof_begin()
-    _lib.call('adn_igemm', C.byref(d), _stream())
     # algorithmic FLOPs 2*M_out*N*K, K = taps*Cin  (S2: 16 taps on B*Hs*Ws pixels; T2: 4 taps on 4x the pixels;
     # S1: ks*ks taps on B*Hs*Ws pixels)
     flops = 2.0 * B * Hs * Ws * N * (ks * ks if geom == GEMM_S1 else 16) * (algo_c if algo_c else d.C0 + d.C1)
-    _lib.annotate(label='igemm', flops=flops)
-    if ev is not None:
-        _prof_end(ev, 'igemm', flops)
+    _launch('igemm', flops, 'adn_igemm', C.byref(d))
 
 
 def _wgrad_desc(dtype, B, Hs, Ws, plain0, plain1, gath0, gath1, dw, workspace, c_valid=0, ks=0):
@@ -169,14 +172,20 @@ def _wgrad_desc(dtype, B, Hs, Ws, plain0, plain1, gath0, gath1, dw, workspace, c
     return d
 
 
-def wgrad_workspace_bytes(dtype, B, Hs, Ws, R0, R1, C0, C1, c_valid=0, ks=0):
-    d = AdnWgradDesc()
+def _wgrad_shape_desc(dtype, B, Hs, Ws, R0, R1, C0, C1, c_valid=0, ks=0, d=None):
+    """A descriptor of the shape alone for the host-only queries (``d``: fill this slot of a descriptor array)."""
+    d = AdnWgradDesc() if d is None else d
     d.c_valid = c_valid
     d.geom, d.ks = (GEMM_S1, ks) if ks else (0, 0)
     d.dtype, d.B, d.Hs, d.Ws, d.R0, d.R1, d.C0, d.C1 = dtype_code(dtype), B, Hs, Ws, R0, R1, C0, C1
     d.plain0 = d.gath0 = d.dw = 1
     d.plain1 = 1 if R1 else None
     d.gath1 = 1 if C1 else None
+    return d
+
+
+def wgrad_workspace_bytes(dtype, B, Hs, Ws, R0, R1, C0, C1, c_valid=0, ks=0):
+    d = _wgrad_shape_desc(dtype, B, Hs, Ws, R0, R1, C0, C1, c_valid, ks)
     lib = _lib.load()
     n = lib.adn_wgrad_workspace_bytes(C.byref(d))
     if n < 0:
@@ -187,32 +196,28 @@ def wgrad_workspace_bytes(dtype, B, Hs, Ws, R0, R1, C0, C1, c_valid=0, ks=0):
 def wgrad_batchable(dtype, B, Hs, Ws, R0, R1, C0, C1, c_valid=0):
     """(class, norm partials) of this k4 weight gradient as a problem of a wgrad_batch launch; class 0 = not batchable,
     problems of one launch share their class (host-only query)."""
-    d = AdnWgradDesc()
-    d.c_valid = c_valid
-    d.geom, d.ks = 0, 0
-    d.dtype, d.B, d.Hs, d.Ws, d.R0, d.R1, d.C0, d.C1 = dtype_code(dtype), B, Hs, Ws, R0, R1, C0, C1
-    d.plain0 = d.gath0 = d.dw = 1
-    d.plain1 = 1 if R1 else None
-    d.gath1 = 1 if C1 else None
+    d = _wgrad_shape_desc(dtype, B, Hs, Ws, R0, R1, C0, C1, c_valid)
     lib = _lib.load()
     return int(lib.adn_wgrad_batchable(C.byref(d))), int(lib.adn_wgrad_batch_sq_count(C.byref(d)))
+
+
+def _wgrad_problems(dtype, B, problems, workspace):
+    """(descriptor array, algorithmic FLOPs) of a list of (Hs, Ws, plain0, plain1, gath0, gath1, dw, sq) k4 problems."""
+    arr = (AdnWgradDesc * len(problems))()
+    flops = 0.0
+    for slot, (Hs, Ws, p0, p1, g0, g1, dw, sq) in zip(arr, problems):
+        d = _wgrad_desc(dtype, B, Hs, Ws, p0, p1, g0, g1, dw, workspace)
+        d.sq_partials = ptr(sq)
+        C.memmove(C.byref(slot), C.byref(d), C.sizeof(AdnWgradDesc))
+        flops += 2.0 * B * Hs * Ws * (d.R0 + d.R1) * 16 * (d.C0 + d.C1)
+    return arr, flops
 
 
 def wgrad_batch(dtype, B, problems, entry='adn_wgrad_batch'):
     """problems: list of (Hs, Ws, plain0, plain1, gath0, gath1, dw, sq): up to 8 weight gradients of ONE class in one
     launch."""
-    arr = (AdnWgradDesc * len(problems))()
-    flops = 0.0
-    for slot, (Hs, Ws, p0, p1, g0, g1, dw, sq) in zip(arr, problems):
-        d = _wgrad_desc(dtype, B, Hs, Ws, p0, p1, g0, g1, dw, None)
-        d.sq_partials = ptr(sq)
-        C.memmove(C.byref(slot), C.byref(d), C.sizeof(AdnWgradDesc))
-        flops += 2.0 * B * Hs * Ws * (d.R0 + d.R1) * 16 * (d.C0 + d.C1)
-    ev = _prof_begin()
-    _lib.call(entry, arr, len(problems), _stream())
-    _lib.annotate(label='wgrad', flops=flops)
-    if ev is not None:
-        _prof_end(ev, 'wgrad', flops)
+    arr, flops = _wgrad_problems(dtype, B, problems, None)
+    _launch('wgrad', flops, entry, arr, len(problems))
 
 
 def wgrad_multi(dtype, B, problems):
@@ -225,40 +230,21 @@ def wgrad_patch_batch_workspace_bytes(dtype, B, shapes):
     """shapes: list of (Hs, Ws, R0, R1, C0, C1).  Bytes of slab scratch of one wgrad_patch_batch launch over them, or -1 when
     some layer is not a patch-staged one (host-only query)."""
     arr = (AdnWgradDesc * len(shapes))()
-    for d, (Hs, Ws, R0, R1, C0, C1) in zip(arr, shapes):
-        d.dtype, d.B, d.Hs, d.Ws, d.R0, d.R1, d.C0, d.C1 = dtype_code(dtype), B, Hs, Ws, R0, R1, C0, C1
-        d.plain0 = d.gath0 = d.dw = 1
-        d.plain1 = 1 if R1 else None
-        d.gath1 = 1 if C1 else None
+    for slot, shape in zip(arr, shapes):
+        _wgrad_shape_desc(dtype, B, *shape, d=slot)
     return int(_lib.load().adn_wgrad_patch_batch_workspace_bytes(arr, len(shapes)))
 
 
 def wgrad_patch_batch(dtype, B, problems, workspace):
     """problems: list of (Hs, Ws, plain0, plain1, gath0, gath1, dw, sq): 2 .. 4 patch-staged weight gradients in one launch
     with 1/n of the pixel splits each (+ one slab sum per problem)."""
-    arr = (AdnWgradDesc * len(problems))()
-    flops = 0.0
-    for slot, (Hs, Ws, p0, p1, g0, g1, dw, sq) in zip(arr, problems):
-        d = _wgrad_desc(dtype, B, Hs, Ws, p0, p1, g0, g1, dw, workspace)
-        d.sq_partials = ptr(sq)
-        C.memmove(C.byref(slot), C.byref(d), C.sizeof(AdnWgradDesc))
-        flops += 2.0 * B * Hs * Ws * (d.R0 + d.R1) * 16 * (d.C0 + d.C1)
-    ev = _prof_begin()
-    _lib.call('adn_wgrad_patch_batch', arr, len(problems), _stream())
-    _lib.annotate(label='wgrad', flops=flops)
-    if ev is not None:
-        _prof_end(ev, 'wgrad', flops)
+    arr, flops = _wgrad_problems(dtype, B, problems, workspace)
+    _launch('wgrad', flops, 'adn_wgrad_patch_batch', arr, len(problems))
 
 
 def wgrad_sq_count(dtype, B, Hs, Ws, R0, R1, C0, C1, c_valid=0, ks=0):
     """Partial sums of dW^2 adn_wgrad leaves behind when asked to (``sq=``); 0 = this layer's kernel has no fused form."""
-    d = AdnWgradDesc()
-    d.c_valid = c_valid
-    d.geom, d.ks = (GEMM_S1, ks) if ks else (0, 0)
-    d.dtype, d.B, d.Hs, d.Ws, d.R0, d.R1, d.C0, d.C1 = dtype_code(dtype), B, Hs, Ws, R0, R1, C0, C1
-    d.plain0 = d.gath0 = d.dw = 1
-    d.plain1 = 1 if R1 else None
-    d.gath1 = 1 if C1 else None
+    d = _wgrad_shape_desc(dtype, B, Hs, Ws, R0, R1, C0, C1, c_valid, ks)
     return int(_lib.load().adn_wgrad_sq_count(C.byref(d)))
 
 
@@ -271,12 +257,8 @@ def wgrad(dtype, B, Hs, Ws, plain0, plain1, gath0, gath1, dw, workspace=None, c_
         if sq.dtype != torch.float64:
             raise TypeError('wgrad: sq must be float64')
         d.sq_partials = ptr(sq)
-    ev = _prof_begin()
-    _lib.call('adn_wgrad', C.byref(d), _stream())
     flops = 2.0 * B * Hs * Ws * (d.R0 + d.R1) * (ks * ks if ks else 16) * (c_valid if c_valid else d.C0 + d.C1)
-    _lib.annotate(label='wgrad', flops=flops)
-    if ev is not None:
-        _prof_end(ev, 'wgrad', flops)
+    _launch('wgrad', flops, 'adn_wgrad', C.byref(d))
 
 
 def pack_weights(master, X, Y, dtype, s2_out=None, t2_out=None, y_pad=None):
@@ -370,12 +352,7 @@ def conv3x3_mx8(B, H, W, in0, sc0, in1, sc1, w8, wsc, N, epi, segs):
     segs[0].fill(d.seg[0])
     if len(segs) > 1:
         segs[1].fill(d.seg[1])
-    ev = _prof_begin()
-    _lib.call('adn_conv3x3_mx8', C.byref(d), _stream())
-    flops = 2.0 * B * H * W * N * 9 * (d.C0 + d.C1)
-    _lib.annotate(label='conv3x3_mx8', flops=flops)
-    if ev is not None:
-        _prof_end(ev, 'conv3x3_mx8', flops)
+    _launch('conv3x3_mx8', 2.0 * B * H * W * N * 9 * (d.C0 + d.C1), 'adn_conv3x3_mx8', C.byref(d))
 
 
 def nchw_to_nhwc(src, dst):

@@ -34,9 +34,10 @@ def child(path):
         out['g/' + k] = eng.grad_view(prm).detach().float().cpu().clone()
     gi = torch.Generator().manual_seed(3)
     for i, lv in enumerate(eng.levels):
-        for name in ('zd', 'ad', 'rd', 'zu', 'ru', 'Gd', 'Gu', 'part_d', 'part_u', 'bpart_d', 'bpart_u', 'mean_d', 'istd_d',
-                     'mean_u', 'istd_u'):
-            t = lv.get(name)
+        bufs = {k: lv.get(k) for k in ('zd', 'ad', 'rd', 'zu', 'ru', 'Gd', 'Gu')}
+        for tag in ('d', 'u'):                     # the statistics live on the level's Side records
+            bufs.update({f'{k}_{tag}': getattr(lv[tag], k) for k in ('part', 'bpart', 'mean', 'istd')})
+        for name, t in bufs.items():
             if torch.is_tensor(t):
                 flat = t.detach().reshape(-1)
                 stride = max(1, flat.numel() // 65536) | 1
