@@ -24,22 +24,33 @@ def _clean(x):
 
 
 def compute_errors(gt, pred, min_depth_threshold=0.0):
+    return compute_errors_traced(gt, pred)[0]
+
+
+def compute_errors_traced(gt, pred):
+    """compute_errors and the way it went: (the seven numbers, dict(branch, eps, eps2, kept)).  branch: 'empty' (no
+    gt != 0), 'gt_le_eps' (no gt above eps), 'pred_le_0' (the all-bad tuple), 'fallback' (keep = gt > eps & pred > 0) or
+    'normal'; eps / eps2 the first and the re-evaluated epsilon, kept the number of pixels in the sums."""
+    zeros = (0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
     gt = np.asarray(gt)
     pred = np.asarray(pred)
     mask = gt != 0.0
     if mask.sum() == 0:
-        return 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0
+        return zeros, dict(branch='empty', eps=None, eps2=None, kept=0)
     p = pred[mask]
     g = gt[mask]
     eps = 1e-3 if g.max() > 1.0 else 1e-6
+    eps1 = eps
+    branch = 'normal'
     keep = (p > eps) & (g > eps)
     if keep.sum() == 0:
         keep = g > eps
         if keep.sum() == 0:
-            return 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0
+            return zeros, dict(branch='gt_le_eps', eps=eps1, eps2=None, kept=0)
         keep = keep & (p > 0)
         if keep.sum() == 0:
-            return 1.0, g.max(), 0.0, 0.0, 0.0, 1.0, g.max()
+            return (1.0, g.max(), 0.0, 0.0, 0.0, 1.0, g.max()), dict(branch='pred_le_0', eps=eps1, eps2=None, kept=0)
+        branch = 'fallback'
     p = p[keep]
     g = g[keep]
     eps = 1e-3 if g.max() > 1.0 else 1e-6
@@ -52,4 +63,5 @@ def compute_errors(gt, pred, min_depth_threshold=0.0):
     abs_rel = _clean(np.mean(np.abs(g - p) / g))
     log_10 = _clean(np.abs(np.log10(np.maximum(g, eps)) - np.log10(pc)).mean())
     mae = _clean(np.abs(g - p).mean())
-    return abs_rel, rmse, a1, a2, a3, log_10, mae
+    return (abs_rel, rmse, a1, a2, a3, log_10, mae), dict(branch=branch, eps=eps1, eps2=eps, kept=int(keep.sum()),
+                                                        thresh=thresh, p=p, g=g)

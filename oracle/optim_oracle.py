@@ -23,6 +23,20 @@ def clip_coef(grads, max_norm=1.0):
     return total, min(coef, 1.0)
 
 
+def sqsum(g):
+    """Sum of squares of one float32 array in float64."""
+    g = np.asarray(g, dtype=np.float64)
+    return float((g * g).sum())
+
+
+def clip_coef_ranges(grads, ranges=(), extra=(), max_norm=1.0):
+    """clip_grad_norm_ over pieces: ``ranges`` = (offset, length) rows of the flat array ``grads`` plus ``extra``, sums of
+    squares somebody else already took.  -> (total norm, min(max_norm / (total + 1e-6), 1))."""
+    s = sum(sqsum(grads[o:o + n]) for o, n in ranges) + float(np.asarray(extra, dtype=np.float64).sum())
+    total = float(np.sqrt(s))
+    return total, min(max_norm / (total + 1e-6), 1.0)
+
+
 def adamw_step(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01,
                decoupled=True, grad_scale=1.0):
     """One Adam/AdamW update (torch.optim single-tensor path, amsgrad=False, maximize=False).
