@@ -151,6 +151,7 @@ _PROTOS = {
     'adn_bn_bwd_apply_mx8': (C.c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),
     'adn_conv3x3_mx8_num_partials': (c_int64, [C.POINTER(AdnMx8ConvDesc)]),
+    'adn_conv3x3_mx8_describe': (C.c_int, [C.POINTER(AdnMx8ConvDesc), C.c_char_p, c_int32]),
     'adn_conv3x3_mx8': (C.c_int, [C.POINTER(AdnMx8ConvDesc), c_void_p]),
     'adn_pack_rows': (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     'adn_pack_transpose_taps': (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,

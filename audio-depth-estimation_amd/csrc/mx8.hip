@@ -496,6 +496,16 @@ extern "C" int64_t adn_conv3x3_mx8_num_partials(const AdnMx8ConvDesc* d) {
   return (int64_t)d->B * d->H * d->W / mx8_rows(d);
 }
 
+extern "C" int adn_conv3x3_mx8_describe(const AdnMx8ConvDesc* d, char* buf, int32_t len) {
+  const int rc = validate(d);
+  if (rc != ADN_OK) return rc;
+  ADN_CHECK_ARG(buf != nullptr && len > 0, "adn_conv3x3_mx8_describe: no buffer");
+  const int bn = mx8_bn(d), rows = mx8_rows(d);
+  snprintf(buf, (size_t)len, "mx bm=%d bn=%d tiles_m=%lld tiles_n=%d", rows, bn, (long long)((int64_t)d->B * d->H * d->W / rows),
+           d->N / bn);
+  return ADN_OK;
+}
+
 extern "C" int adn_conv3x3_mx8(const AdnMx8ConvDesc* d, void* stream) {
   const int rc = validate(d);
   if (rc != ADN_OK) return rc;

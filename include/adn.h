@@ -226,6 +226,10 @@ typedef struct {
   AdnEpiSeg seg[2];    /* bf16 tensors                                                             */
 } AdnMx8ConvDesc;
 int64_t adn_conv3x3_mx8_num_partials(const AdnMx8ConvDesc* d);   /* stats partial rows = B*H*W / rows per workgroup (128 | 256) */
+/* Host only: the kernel form of this descriptor as one line of text in buf, "mx bm=<128|256> bn=<64|128> tiles_m=<..>
+ * tiles_n=<..>" (bm x bn = output pixels x columns per workgroup; tiles_m = the partial rows above).  Validates as the
+ * launch does and launches nothing. */
+int adn_conv3x3_mx8_describe(const AdnMx8ConvDesc* d, char* buf, int32_t len);
 int adn_conv3x3_mx8(const AdnMx8ConvDesc* d, void* stream);
 
 /* ---- DoubleConv U-Net family (DoubleConv / Down / Up: binaural_attention_model.py:22-78, identical copies
