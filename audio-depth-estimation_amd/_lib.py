@@ -94,6 +94,25 @@ class AdnCoarseLoss(C.Structure):
     ]
 
 
+class AdnCoarseDecode(C.Structure):
+    _fields_ = [
+        ('logits', c_void_p), ('dtype', c_int32), ('nb', c_int32), ('ld', c_int32),
+        ('pixels', c_int64),
+        ('centers', c_void_p),
+        ('mean', c_void_p), ('hard', c_void_p), ('stdev', c_void_p), ('entropy', c_void_p), ('confidence', c_void_p),
+        ('argmax', c_void_p),
+    ]
+
+
+class AdnCoarseEvalStats(C.Structure):
+    _fields_ = [
+        ('argmax', c_void_p), ('bins', c_void_p), ('confidence', c_void_p), ('stdev', c_void_p), ('entropy', c_void_p),
+        ('mean', c_void_p), ('gt', c_void_p),
+        ('pixels', c_int64),
+        ('workspace', c_void_p), ('workspace_bytes', c_int64),
+    ]
+
+
 class AdnDualRegLoss(C.Structure):
     _fields_ = [
         ('coarse', c_void_p), ('offset', c_void_p), ('gt', c_void_p), ('n_valid', c_void_p),
@@ -293,6 +312,10 @@ _PROTOS = {
     'adn_coarse_loss': (C.c_int, [C.POINTER(AdnCoarseLoss), c_void_p]),
     'adn_coarse_loss_finish': (C.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p,
                                          c_void_p]),
+    'adn_coarse_decode': (C.c_int, [C.POINTER(AdnCoarseDecode), c_void_p]),
+    'adn_coarse_eval_stats_workspace_bytes': (c_int64, [c_int64]),
+    'adn_coarse_eval_stats': (C.c_int, [C.POINTER(AdnCoarseEvalStats), c_void_p]),
+    'adn_coarse_eval_finish': (C.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     'adn_dualreg_loss_workspace_bytes': (c_int64, [c_int64]),
     'adn_dualreg_loss': (C.c_int, [C.POINTER(AdnDualRegLoss), c_void_p]),
     'adn_dualreg_loss_finish': (C.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_float, c_float, c_float,

@@ -11,6 +11,8 @@ CoarseLiteEngine runs CoarseDepthLite (:199-287) through the same engine: only t
 """
 from __future__ import annotations
 
+from collections import namedtuple
+
 import torch
 
 from . import kernels as K
@@ -44,6 +46,7 @@ class ClassLogits:
     def alloc_centers(self):
         self.centers = torch.empty(self.module.n_bins, dtype=torch.float32, device=self.dev)
         self._bridge = None
+        self._planes = None
 
     def load_centers(self):
         self.centers.copy_(self.module.bin_centers.detach().to(torch.float32).reshape(-1))
@@ -57,6 +60,25 @@ class ClassLogits:
             self._bridge = (torch.empty(self.B, lg.C, **f32), torch.empty(self.B, lg.C, **f32),
                             torch.empty(self.B, lg.H, lg.W, lg.C, **f32))
         return self._bridge
+
+    def decode_head(self, mean):
+        """ONE adn_coarse_decode pass over ``logits``: the expectation into ``mean`` (the engine's depth plane, the bits
+        the forward-only adn_coarse_loss writes there) and the rest of the distribution into the per-shape planes."""
+        if self._planes is None:
+            lg = self.logits
+            plane = lambda dt: torch.empty(self.B, 1, lg.H, lg.W, dtype=dt, device=self.dev)
+            self._planes = {k: plane(torch.float32) for k in ('hard', 'std', 'entropy', 'confidence')}
+            self._planes['argmax'] = plane(torch.int32)
+        pl = self._planes
+        pl['mean'] = mean
+        K.coarse_decode(self.logits.data, self.module.n_bins, self.centers,
+                        **{k: pl[k].view(-1) for k in CoarseDistribution._fields})
+
+    def decode(self, x, training=False):
+        """The tape up to the logits, then the distribution read out instead of collapsed: -> dict of the engine's own
+        planes [B,1,H,W] (mean, hard, std, entropy, confidence f32, argmax int32; the hybrid engine adds offset, final)."""
+        self.forward_net(x, training, decode=True)
+        return self._planes
 
     def logits_nchw(self):
         lg = self.logits
@@ -124,14 +146,17 @@ class CoarseDepthEngine(ClassLogits, DCEngine):
         self.depth = torch.empty(B, 1, H, W, dtype=torch.float32, device=self.dev)
         self.alloc_centers()
 
-    def forward_net(self, x, training, argmax=None, head=True):
+    def forward_net(self, x, training, argmax=None, head=True, decode=False):
         """-> (logits NHWC in the compute dtype, depth f32 [B,1,H,W]); both are the engine's own buffers.  ``head=False``
         (the fused trainer): the softmax expectation is left to the caller's own adn_coarse_loss pass, which writes
-        ``depth`` together with the loss and the gradient, so the logits are read once per step."""
+        ``depth`` together with the loss and the gradient, so the logits are read once per step.  ``decode=True``:
+        ``depth`` comes from the adn_coarse_decode pass that also fills the distribution planes."""
         self._begin_forward(x)
         self._forward_ops(self.ops, training)
         self.load_centers()
-        if head:
+        if decode:
+            self.decode_head(self.depth)
+        elif head:
             K.coarse_loss(self.logits.data, self.module.n_bins, self.centers, self.depth, argmax=argmax)
         return self.logits.data, self.depth
 
@@ -208,6 +233,19 @@ def run_coarse_hard(engine, x, training):
         engine.forward_net(x, training, argmax=idx)
         centers = engine.module.bin_centers
         return centers[idx.long()].view(x.shape[0], 1, x.shape[2], x.shape[3])
+
+
+CoarseDistribution = namedtuple('CoarseDistribution', 'mean hard std entropy confidence argmax')
+HybridDistribution = namedtuple('HybridDistribution', CoarseDistribution._fields + ('offset', 'final'))
+
+
+def run_distribution(engine, x, training, result=CoarseDistribution):
+    """predict_distribution(x): clones of the planes of ``engine.decode``, each [B,1,H,W]."""
+    if not engine._bound():              # as run_engine: the refusals of forward come in forward's order
+        engine.bind_parameters()
+    with torch.no_grad():
+        planes = engine.decode(x, training)
+        return result(*(planes[k].clone() for k in result._fields))
 
 
 class BinTargets:

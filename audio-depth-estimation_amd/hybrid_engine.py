@@ -56,18 +56,24 @@ class HybridEngine(ClassLogits, OffsetBranch, DCEngine):
         self.final = torch.empty(B, 1, H, W, **f32)
         self.alloc_centers()
 
-    def forward_net(self, x, training, head=True):
+    def forward_net(self, x, training, head=True, decode=False):
         """-> (logits NHWC in the compute dtype, coarse, offset, final), the maps f32 [B,1,H,W]; all four are the engine's
         own buffers.  ``head=False`` (the fused trainer): final is left to the caller's own adn_hybrid_loss pass, which
-        writes it together with the loss and the gradients."""
+        writes it together with the loss and the gradients.  ``decode=True``: the adn_coarse_decode pass stands in for
+        the forward-only adn_coarse_loss; its mean plane is the coarse depth the offset branch reads."""
         self._begin_forward(x)
         self._forward_ops(self.ops_coarse, training)
         self.class_op.fwd(self, training)
         self.load_centers()
-        K.coarse_loss(self.logits.data, self.module.n_bins, self.centers, self.coarse)        # forward only
+        if decode:
+            self.decode_head(self.coarse)
+        else:
+            K.coarse_loss(self.logits.data, self.module.n_bins, self.centers, self.coarse)        # forward only
         offset = self.forward_offset(self.coarse, training)
         if head:
             K.dualreg_loss(self.coarse.view(-1), offset.view(-1), self.final.view(-1))
+        if decode:
+            self._planes.update(offset=offset, final=self.final)
         return self.logits.data, self.coarse, offset, self.final
 
     def run(self, x, training):

@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import AdnAttnDesc, AdnCoarseLoss, AdnDistillSmall, AdnDualRegLoss, AdnHybridLoss  # noqa: E402
+from ._lib import AdnAttnDesc, AdnCoarseDecode, AdnCoarseEvalStats, AdnCoarseLoss, AdnDistillSmall, AdnDualRegLoss, AdnHybridLoss  # noqa: E402
 from ._lib import (ADN_BF16, ADN_F32, EPI_ACT, EPI_ADD, EPI_BWD, EPI_FINAL, EPI_RAW, EPI_Z_STATS, GEMM_S1, GEMM_S2, GEMM_T2,
                    AdnEpiSeg, AdnIgemmDesc, AdnMx8ConvDesc, AdnWgradDesc, ptr)
 
@@ -1227,6 +1227,64 @@ def coarse_loss_finish(workspace, pixels, sums, n_valid, pixels_global, ce_weigh
     _dev(workspace, sums, n_valid, terms)
     _lib.call('adn_coarse_loss_finish', ptr(workspace), int(pixels), ptr(sums), ptr(n_valid), int(pixels_global),
               float(ce_weight), float(reg_weight), ptr(terms), _stream())
+
+
+EVAL_SUMS, EVAL_OUT = 41, 39          # f64 lengths of adn_coarse_eval_finish's sums and out (include/adn.h)
+EVAL_FIELDS = ('n_valid', 'top1', 'within1', 'mean_bin_error', 'mean_std', 'mean_entropy', 'mean_confidence',
+               'std_error_corr', 'ece')                     # out[:9]; out[9:] is the reliability table [10][3]
+
+
+def coarse_decode(logits, nb, centers, mean=None, hard=None, std=None, entropy=None, confidence=None, argmax=None):
+    """logits [..., ld] (bf16 / f32, ld >= nb), centers f32 [nb] -> the given planes, f32 [pixels] (argmax int32), each
+    optional; see adn_coarse_decode."""
+    ld = logits.shape[-1]
+    pixels = logits.numel() // ld
+    _dev(logits, centers, mean, hard, std, entropy, confidence, argmax)
+    for name, t, dt in (('centers', centers, torch.float32), ('mean', mean, torch.float32), ('hard', hard, torch.float32),
+                        ('std', std, torch.float32), ('entropy', entropy, torch.float32),
+                        ('confidence', confidence, torch.float32), ('argmax', argmax, torch.int32)):
+        if t is not None and (t.dtype != dt or not t.is_contiguous()):
+            raise RuntimeError(f'coarse_decode: {name} must be contiguous {dt}')
+        if t is not None and name != 'centers' and t.numel() != pixels:
+            raise RuntimeError(f'coarse_decode: {name} has {t.numel()} elements for {pixels} pixels')
+    if centers.numel() != nb or not logits.is_contiguous():
+        raise RuntimeError('coarse_decode: centers must hold n_bins values; logits contiguous')
+    d = AdnCoarseDecode()
+    d.logits, d.dtype, d.nb, d.ld, d.pixels = ptr(logits), dtype_code(logits.dtype), nb, ld, pixels
+    d.centers, d.mean, d.hard, d.stdev = ptr(centers), ptr(mean), ptr(hard), ptr(std)
+    d.entropy, d.confidence, d.argmax = ptr(entropy), ptr(confidence), ptr(argmax)
+    _lib.call('adn_coarse_decode', C.byref(d), _stream())
+
+
+def coarse_eval_stats_workspace_bytes(pixels):
+    return _lib.load().adn_coarse_eval_stats_workspace_bytes(pixels)
+
+
+def coarse_eval_stats(argmax, bins, confidence, std, entropy, mean, gt, workspace):
+    """The planes of coarse_decode, the target bins (int32) and gt (f32), [pixels] each -> per-block partials in
+    ``workspace``; see adn_coarse_eval_stats."""
+    pixels = gt.numel()
+    _dev(argmax, bins, confidence, std, entropy, mean, gt, workspace)
+    for name, t, dt in (('argmax', argmax, torch.int32), ('bins', bins, torch.int32), ('confidence', confidence, torch.float32),
+                        ('std', std, torch.float32), ('entropy', entropy, torch.float32), ('mean', mean, torch.float32),
+                        ('gt', gt, torch.float32)):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() != pixels:
+            raise RuntimeError(f'coarse_eval_stats: {name} must be contiguous {dt} with {pixels} elements')
+    d = AdnCoarseEvalStats()
+    d.argmax, d.bins, d.confidence, d.stdev = ptr(argmax), ptr(bins), ptr(confidence), ptr(std)
+    d.entropy, d.mean, d.gt, d.pixels = ptr(entropy), ptr(mean), ptr(gt), pixels
+    d.workspace, d.workspace_bytes = ptr(workspace), _nbytes(workspace)
+    _lib.call('adn_coarse_eval_stats', C.byref(d), _stream())
+
+
+def coarse_eval_finish(workspace, pixels, sums, out=None):
+    """workspace None: sums f64[EVAL_SUMS] are taken as given (added up over batches by the caller); out f64[EVAL_OUT] or
+    None."""
+    _dev(workspace, sums, out)
+    for name, t, n in (('sums', sums, EVAL_SUMS), ('out', out, EVAL_OUT)):
+        if t is not None and (t.dtype != torch.float64 or not t.is_contiguous() or t.numel() < n):
+            raise RuntimeError(f'coarse_eval_finish: {name} must be contiguous float64 with {n} elements')
+    _lib.call('adn_coarse_eval_finish', ptr(workspace), int(pixels), ptr(sums), ptr(out), _stream())
 
 
 # ---- dual-regression coarse-depth family (csrc/dualreg.hip) --------------------------------------------------------

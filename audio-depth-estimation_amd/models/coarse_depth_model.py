@@ -155,6 +155,14 @@ class CoarseDepthUNet(nn.Module):
         from ..coarse_engine import run_coarse_hard
         return run_coarse_hard(self.engine(), x, self.training)
 
+    def predict_distribution(self, x: torch.Tensor):
+        """The per-pixel predictive distribution of the class head in one adn_coarse_decode pass (call under
+        ``torch.no_grad()``): named tuple ``(mean, hard, std, entropy, confidence, argmax)``, each [B, 1, H, W] -- the
+        softmax expectation (= ``forward(x)``'s depth), the centre of the first-maximum bin, the distribution's standard
+        deviation over the bin centres, its entropy in nats, max_k p_k, and the first-maximum bin (int32)."""
+        from ..coarse_engine import run_distribution
+        return run_distribution(self.engine(), x, self.training)
+
     def get_num_params(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
 
@@ -209,6 +217,14 @@ class CoarseDepthLite(nn.Module):
         hang off one autograd node, so the reference's ``criterion(logits, depth, ...)['total'].backward()`` loop works."""
         from ..coarse_engine import run_coarse
         return run_coarse(self.engine(), x, self.training)
+
+    def predict_distribution(self, x: torch.Tensor):
+        """The per-pixel predictive distribution of the class head in one adn_coarse_decode pass (call under
+        ``torch.no_grad()``): named tuple ``(mean, hard, std, entropy, confidence, argmax)``, each [B, 1, H, W] -- the
+        softmax expectation (= ``forward(x)``'s depth), the centre of the first-maximum bin, the distribution's standard
+        deviation over the bin centres, its entropy in nats, max_k p_k, and the first-maximum bin (int32)."""
+        from ..coarse_engine import run_distribution
+        return run_distribution(self.engine(), x, self.training)
 
     def get_num_params(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
@@ -396,6 +412,13 @@ class CoarseWithOffsetModel(nn.Module):
 
     def predict_depth(self, x: torch.Tensor) -> torch.Tensor:
         return self.forward(x)[3]
+
+    def predict_distribution(self, x: torch.Tensor):
+        """The per-pixel predictive distribution of the class head in one adn_coarse_decode pass (call under
+        ``torch.no_grad()``): named tuple ``(mean, hard, std, entropy, confidence, argmax, offset, final)``, each
+        [B, 1, H, W]; ``mean`` is the coarse depth the offset branch read, ``final = mean + offset``."""
+        from ..coarse_engine import HybridDistribution, run_distribution
+        return run_distribution(self.engine(), x, self.training, HybridDistribution)
 
     def get_num_params(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)

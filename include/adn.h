@@ -753,6 +753,54 @@ int adn_coarse_loss(const AdnCoarseLoss* d, void* stream);
  * pixels_global, regression = sums[1] / n_valid (NaN when n_valid == 0), total = ce_weight ce + reg_weight regression). */
 int adn_coarse_loss_finish(const void* workspace, int64_t pixels, double* sums, const double* n_valid,
                            int64_t pixels_global, float ce_weight, float reg_weight, float* terms, void* stream);
+/* adn_coarse_decode: ONE pass over the class logits [pixels][ld] (dtype, nb <= ld, 2 <= nb <= 512): the per-pixel
+ * distribution p = softmax(x) over the bin centres c, read out instead of collapsed.  With d_k = x_k - max, e_k = exp d_k,
+ * Z = sum e_k; every output is f32 [pixels] (argmax int32) and optional, at least one must be given:
+ *   mean       = sum p_k c_k            the bits of the forward-only adn_coarse_loss's depth
+ *   argmax     = first maximum          the bits of adn_coarse_loss's argmax
+ *   hard       = c[argmax]
+ *   stdev      = sqrt(sum p_k (c_k - mean)^2), the second moment taken about the mean (never sum p c^2 - mean^2)
+ *   entropy    = ln Z - sum p_k d_k     nats; both terms >= 0
+ *   confidence = max_k p_k = 1 / Z
+ * Same grid and row layouts as adn_coarse_loss; the logits are read once. */
+typedef struct {
+  const void* logits;
+  int32_t dtype, nb, ld;
+  int64_t pixels;
+  const float* centers;              /* [nb] */
+  float* mean;                       /* [pixels] or NULL, as every output */
+  float* hard;
+  float* stdev;
+  float* entropy;
+  float* confidence;
+  int32_t* argmax;
+} AdnCoarseDecode;
+int adn_coarse_decode(const AdnCoarseDecode* d, void* stream);
+/* adn_coarse_eval_stats: one pass over adn_coarse_decode's planes, the target bins t (adn_coarse_targets) and gt; a pixel
+ * counts when gt > 0 (the family's training mask).  Per-block f64 partials of 41 sums go into the workspace
+ * (adn_coarse_eval_stats_workspace_bytes(pixels)), with s = stdev, a = |mean - gt| and h = [argmax == t]:
+ *   [0] n  [1] sum h  [2] sum [|argmax - t| <= 1]  [3] sum |argmax - t|  [4] sum s  [5] sum entropy  [6] sum confidence
+ *   [7] sum a  [8] sum s^2  [9] sum a^2  [10] sum s a
+ *   [11 + 3 b ..] reliability bin b = min(9, floor(confidence * 10)) (f32): count, sum confidence, sum h     b = 0 .. 9 */
+typedef struct {
+  const int32_t* argmax;             /* [pixels], as every operand */
+  const int32_t* bins;
+  const float* confidence;
+  const float* stdev;
+  const float* entropy;
+  const float* mean;
+  const float* gt;
+  int64_t pixels;
+  void* workspace;
+  int64_t workspace_bytes;
+} AdnCoarseEvalStats;
+int64_t adn_coarse_eval_stats_workspace_bytes(int64_t pixels);
+int adn_coarse_eval_stats(const AdnCoarseEvalStats* d, void* stream);
+/* workspace != NULL: reduce the partials adn_coarse_eval_stats left for `pixels` pixels into sums f64[41]; NULL: take sums
+ * as given (the caller added up the sums of several batches; pixels unused).  out != NULL: out f64[39] = (n_valid, top1,
+ * within1, mean_bin_error, mean_std, mean_entropy, mean_confidence, std_error_corr = Pearson(s, a), NaN when either
+ * variance is 0, ece = sum_b n_b / n |acc_b - conf_b|, then the 30 table sums as stored).  n == 0: every ratio is NaN. */
+int adn_coarse_eval_finish(const void* workspace, int64_t pixels, double* sums, double* out, void* stream);
 
 /* Dual-regression coarse-depth family (DualRegressionModel / DualRegressionLoss, models/coarse_depth_model.py): the loss
  * tail behind the two 1x1 heads.  f32 arithmetic, f64 final reductions, no atomics, bit-reproducible.
