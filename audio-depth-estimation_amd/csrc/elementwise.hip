@@ -1,6 +1,6 @@
 // Memory-bound helpers around the implicit GEMMs: weight packing, NCHW<->NHWC boundary
 // conversion, BatchNorm finalize / apply passes.  All are streaming kernels (HBM roofline),
-// 16-byte accesses where the layout allows, grid capped at ~2048 blocks with grid-stride loops.
+// 16-byte accesses where the layout allows, grid-stride loops over a grid capped at 4096 blocks (BN apply kernels: 1024).
 #include "epilogue.h"
 #include "mx8_quant.h"
 
