@@ -525,20 +525,20 @@ extern "C" int64_t adn_pool_workspace_bytes(int32_t B, int32_t HW, int32_t C, in
 extern "C" int adn_pool(const void* x, const void* y, int32_t B, int32_t HW, int32_t C, int32_t ld, int32_t nq,
                         int32_t dtype, float scale, float* out, void* workspace, int64_t workspace_bytes, void* stream) {
   ADN_CHECK_ARG(x && out && B > 0 && HW > 0 && C > 0 && ld >= C && (nq == 1 || (nq == 3 && y)), "adn_pool: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_pool: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_pool", dtype);
   ADN_CHECK_ARG(workspace && workspace_bytes >= adn_pool_workspace_bytes(B, HW, C, nq), "adn_pool: workspace too small");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int P = pool_parts(HW);
   float* part = reinterpret_cast<float*>(workspace);
   const dim3 grid(P, B);
-  if (dtype == ADN_BF16) {
-    if (nq == 1) hipLaunchKernelGGL((rowsum_partial<uint16_t, 1>), grid, dim3(256), 0, st, x, y, HW, C, ld, part);
-    else hipLaunchKernelGGL((rowsum_partial<uint16_t, 3>), grid, dim3(256), 0, st, x, y, HW, C, ld, part);
-  } else {
-    if (nq == 1) hipLaunchKernelGGL((rowsum_partial<float, 1>), grid, dim3(256), 0, st, x, y, HW, C, ld, part);
-    else hipLaunchKernelGGL((rowsum_partial<float, 3>), grid, dim3(256), 0, st, x, y, HW, C, ld, part);
-  }
-  ADN_CHECK_LAUNCH();
+  const int rc = adn_by_dtype("adn_pool", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (nq == 1) hipLaunchKernelGGL((rowsum_partial<T, 1>), grid, dim3(256), 0, st, x, y, HW, C, ld, part);
+    else hipLaunchKernelGGL((rowsum_partial<T, 3>), grid, dim3(256), 0, st, x, y, HW, C, ld, part);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
+  if (rc != ADN_OK) return rc;
   hipLaunchKernelGGL(rowsum_final, dim3((unsigned)adn_cdiv(nq * C, 256), B), dim3(256), 0, st, part, P, nq * C, scale, out);
   ADN_CHECK_LAUNCH();
   return ADN_OK;
@@ -580,31 +580,38 @@ extern "C" int adn_dropout_mask(uint8_t* mask, int64_t n, float p, uint64_t seed
 extern "C" int adn_bcast_add(void* gx, const float* dg, int32_t B, int32_t HW, int32_t C, float scale, int32_t accumulate,
                              int32_t dtype, void* stream) {
   ADN_CHECK_ARG(gx && dg && B > 0 && HW > 0 && C > 0, "adn_bcast_add: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_bcast_add: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_bcast_add", dtype);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t n = (int64_t)B * HW * C;
-  if (dtype == ADN_BF16) hipLaunchKernelGGL((bcast_add_kernel<uint16_t>), dim3(blocks_for(n)), dim3(256), 0, st, gx, dg, HW, C, scale, accumulate, n);
-  else hipLaunchKernelGGL((bcast_add_kernel<float>), dim3(blocks_for(n)), dim3(256), 0, st, gx, dg, HW, C, scale, accumulate, n);
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype("adn_bcast_add", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((bcast_add_kernel<T>), dim3(blocks_for(n)), dim3(256), 0, st, gx, dg, HW, C, scale, accumulate, n);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int adn_bins_fwd(const void* logits, const float* centers, int32_t B, int32_t HW, int32_t nb, int32_t dtype,
                             float* base, void* stream) {
   ADN_CHECK_ARG(logits && centers && base && B > 0 && HW > 0 && nb > 0 && nb <= kMaxBins, "adn_bins_fwd: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_bins_fwd: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_bins_fwd", dtype);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t pixels = (int64_t)B * HW;
   const dim3 grid(blocks_for(pixels * 64));
   if (dtype == ADN_BF16 && (nb == 128 || nb == 64) && (reinterpret_cast<uintptr_t>(logits) & 15) == 0) {
-    const uint16_t* lg = reinterpret_cast<const uint16_t*>(logits);
+    const uint16_t* lg = adn_as<uint16_t>(logits);          // bf16-only fast path: 16-byte loads of whole bin rows
     const dim3 gv(blocks_for(pixels * (nb / 8)));
     if (nb == 128) hipLaunchKernelGGL((bins_fwd_vec_kernel<16>), gv, dim3(256), 0, st, lg, centers, pixels, HW, base);
     else hipLaunchKernelGGL((bins_fwd_vec_kernel<8>), gv, dim3(256), 0, st, lg, centers, pixels, HW, base);
-  } else if (dtype == ADN_BF16) hipLaunchKernelGGL((bins_fwd_kernel<uint16_t>), grid, dim3(256), 0, st, logits, centers, pixels, HW, nb, base);
-  else hipLaunchKernelGGL((bins_fwd_kernel<float>), grid, dim3(256), 0, st, logits, centers, pixels, HW, nb, base);
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  }
+  return adn_by_dtype("adn_bins_fwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((bins_fwd_kernel<T>), grid, dim3(256), 0, st, logits, centers, pixels, HW, nb, base);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int64_t adn_bins_bwd_workspace_bytes(int32_t B, int32_t HW, int32_t nb) {
@@ -617,18 +624,21 @@ extern "C" int adn_bins_bwd(const void* logits, const float* centers, const floa
                             float* dcent, int32_t dcent_accumulate, void* workspace, int64_t workspace_bytes, void* stream) {
   ADN_CHECK_ARG(logits && centers && base && dbase && dlogits && dcent && B > 0 && HW > 0 && nb > 0 && nb <= kMaxBins,
                 "adn_bins_bwd: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_bins_bwd: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_bins_bwd", dtype);
   ADN_CHECK_ARG(workspace && workspace_bytes >= adn_bins_bwd_workspace_bytes(B, HW, nb), "adn_bins_bwd: workspace too small");
   ADN_CHECK_ARG(!dcent_accumulate, "adn_bins_bwd: accumulate into dcent is done by the caller's small-terms kernel");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int P = pool_parts(HW);
   float* part = reinterpret_cast<float*>(workspace);
   const dim3 grid(P, B);
-  if (dtype == ADN_BF16)
-    hipLaunchKernelGGL((bins_bwd_kernel<uint16_t>), grid, dim3(256), 0, st, logits, centers, base, dbase, dmean, 1.f / HW, HW, nb, dlogits, part);
-  else
-    hipLaunchKernelGGL((bins_bwd_kernel<float>), grid, dim3(256), 0, st, logits, centers, base, dbase, dmean, 1.f / HW, HW, nb, dlogits, part);
-  ADN_CHECK_LAUNCH();
+  const int rc = adn_by_dtype("adn_bins_bwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((bins_bwd_kernel<T>), grid, dim3(256), 0, st, logits, centers, base, dbase, dmean, 1.f / HW, HW, nb,
+                       dlogits, part);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
+  if (rc != ADN_OK) return rc;
   hipLaunchKernelGGL(rowsum_final, dim3((unsigned)adn_cdiv(nb, 256), B), dim3(256), 0, st, part, P, nb, 1.0f, dcent);
   ADN_CHECK_LAUNCH();
   return ADN_OK;
@@ -663,13 +673,15 @@ extern "C" int adn_distill_pix_grad(const float* base, const float* resid, const
 extern "C" int adn_featcos_grad(const void* a, const void* r, const float* stats, int32_t B, int32_t HW, int32_t C,
                                 int32_t dtype, float coef, void* ga, void* stream) {
   ADN_CHECK_ARG(a && r && stats && ga && B > 0 && HW > 0 && C > 0, "adn_featcos_grad: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_featcos_grad: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_featcos_grad", dtype);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t n = (int64_t)B * HW * C;
-  if (dtype == ADN_BF16) hipLaunchKernelGGL((featcos_grad_kernel<uint16_t>), dim3(blocks_for(n)), dim3(256), 0, st, a, r, stats, HW, C, coef, ga, n);
-  else hipLaunchKernelGGL((featcos_grad_kernel<float>), dim3(blocks_for(n)), dim3(256), 0, st, a, r, stats, HW, C, coef, ga, n);
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype("adn_featcos_grad", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((featcos_grad_kernel<T>), dim3(blocks_for(n)), dim3(256), 0, st, a, r, stats, HW, C, coef, ga, n);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int adn_distill_small(const AdnDistillSmall* d, void* stream) {

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/adn.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
@@ -30,6 +32,36 @@ void adn_set_error(const char* fmt, ...);
       return ADN_ERR_LAUNCH;                                                 \
     }                                                                        \
   } while (0)
+
+// ---- entry points that take an activation dtype -------------------------------------------------
+// Such an entry point (1) checks the code with ADN_CHECK_DTYPE, in its place among the other argument checks, (2) writes
+// its launch ONCE inside adn_by_dtype(who, dtype, [&](auto t) { using T = decltype(t); ...; return ADN_OK; }), where T
+// is the element type (uint16_t = raw bf16 bits for ADN_BF16, float for ADN_F32), and (3) types its void pointers with
+// adn_as<T>(p).  The lambda returns a status, so ADN_CHECK_LAUNCH() works inside it; an unknown code never reaches a
+// kernel: the dispatcher itself answers "<who>: bad dtype <n>" / ADN_ERR_ARG.
+#define ADN_CHECK_DTYPE(who, dtype) \
+  ADN_CHECK_ARG((dtype) == ADN_F32 || (dtype) == ADN_BF16, "%s: bad dtype %d", (who), (int)(dtype))
+
+template <typename T> static inline T* adn_as(void* p) { return reinterpret_cast<T*>(p); }
+template <typename T> static inline const T* adn_as(const void* p) { return reinterpret_cast<const T*>(p); }
+
+template <typename F>
+static inline int adn_by_dtype(const char* who, int dtype, F&& launch) {
+  if (dtype == ADN_BF16) return launch(uint16_t{});
+  if (dtype == ADN_F32) return launch(float{});
+  adn_set_error("%s: bad dtype %d", who, dtype);
+  return ADN_ERR_ARG;
+}
+// ... and the vector width of the NHWC streaming kernels: the lambda also gets V = 8 (vec8, as a rule C % 8 == 0:
+// 16-byte accesses) or 1 as a compile-time constant,
+// [&](auto t, auto v) { using T = decltype(t); constexpr int V = decltype(v)::value; ... }
+template <typename F>
+static inline int adn_by_dtype_v(const char* who, int dtype, bool vec8, F&& launch) {
+  return adn_by_dtype(who, dtype, [&](auto t) {
+    return vec8 ? launch(t, std::integral_constant<int, 8>{}) : launch(t, std::integral_constant<int, 1>{});
+  });
+}
+static inline int adn_dtype_bytes(int dtype) { return dtype == ADN_BF16 ? 2 : 4; }
 
 // ---- element conversion ------------------------------------------------------------------
 __device__ __forceinline__ float bf16_bits_to_f32(uint16_t h) {

@@ -339,7 +339,7 @@ __global__ __launch_bounds__(256) void gate_bwd_finish_kernel(const double* part
 
 int avalidate(const AdnAttnDesc* d, bool bwd) {
   ADN_CHECK_ARG(d != nullptr, "adn_attn: null descriptor");
-  ADN_CHECK_ARG(d->dtype == ADN_F32 || d->dtype == ADN_BF16, "adn_attn: bad dtype %d", d->dtype);
+  ADN_CHECK_DTYPE("adn_attn", d->dtype);
   ADN_CHECK_ARG(d->B2 > 0 && d->N > 0 && d->dqk > 0 && d->dv > 0, "adn_attn: bad shape");
   ADN_CHECK_ARG(d->dqk <= kMaxDqk && d->dv <= kMaxDv, "adn_attn: head dims %d/%d exceed %d/%d", d->dqk, d->dv, kMaxDqk,
                 kMaxDv);
@@ -389,10 +389,12 @@ extern "C" int adn_attn_fwd(const AdnAttnDesc* d, void* stream) {
   }
   const AttnParams p = to_params(d);
   const dim3 grid((unsigned)adn_cdiv(d->N, kWaves), d->B2);
-  if (d->dtype == ADN_BF16) hipLaunchKernelGGL((attn_fwd_generic<uint16_t>), grid, dim3(256), 0, st, p);
-  else hipLaunchKernelGGL((attn_fwd_generic<float>), grid, dim3(256), 0, st, p);
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype("adn_attn", d->dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((attn_fwd_generic<T>), grid, dim3(256), 0, st, p);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int64_t adn_attn_bwd_workspace_bytes(const AdnAttnDesc* d) {
@@ -408,26 +410,26 @@ extern "C" int adn_attn_bwd(const AdnAttnDesc* d, void* stream) {
   unsigned rb = (unsigned)adn_cdiv(rows, kWaves);
   if (rb > 4096) rb = 4096;
   float* dsum = reinterpret_cast<float*>(d->workspace);
-  if (d->dtype == ADN_BF16)
-    hipLaunchKernelGGL((attn_rowdot<uint16_t>), dim3(rb), dim3(256), 0, st, d->dout, d->ld_do, d->o, d->ld_o, rows, d->dv, dsum);
-  else
-    hipLaunchKernelGGL((attn_rowdot<float>), dim3(rb), dim3(256), 0, st, d->dout, d->ld_do, d->o, d->ld_o, rows, d->dv, dsum);
-  ADN_CHECK_LAUNCH();
+  rc = adn_by_dtype("adn_attn", d->dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((attn_rowdot<T>), dim3(rb), dim3(256), 0, st, d->dout, d->ld_do, d->o, d->ld_o, rows, d->dv, dsum);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
+  if (rc != ADN_OK) return rc;
   if (adn_attn_mfma_bwd(d, st) == 1) {
     ADN_CHECK_LAUNCH();
     return ADN_OK;
   }
   const AttnParams p = to_params(d);
   const dim3 grid((unsigned)adn_cdiv(d->N, kWaves), d->B2);
-  if (d->dtype == ADN_BF16) {
-    hipLaunchKernelGGL((attn_bwd_dq_generic<uint16_t>), grid, dim3(256), 0, st, p);
-    hipLaunchKernelGGL((attn_bwd_dkv_generic<uint16_t>), grid, dim3(256), 0, st, p);
-  } else {
-    hipLaunchKernelGGL((attn_bwd_dq_generic<float>), grid, dim3(256), 0, st, p);
-    hipLaunchKernelGGL((attn_bwd_dkv_generic<float>), grid, dim3(256), 0, st, p);
-  }
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype("adn_attn", d->dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((attn_bwd_dq_generic<T>), grid, dim3(256), 0, st, p);
+    hipLaunchKernelGGL((attn_bwd_dkv_generic<T>), grid, dim3(256), 0, st, p);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int64_t adn_channel_sum_workspace_bytes(int64_t rows, int32_t C) {
@@ -440,7 +442,7 @@ extern "C" int64_t adn_channel_sum_workspace_bytes(int64_t rows, int32_t C) {
 extern "C" int adn_channel_sum(const void* x, int64_t rows, int32_t C, int32_t ld, int32_t dtype, float* out,
                                void* workspace, int64_t workspace_bytes, void* stream) {
   ADN_CHECK_ARG(x && out && rows > 0 && C > 0 && ld >= C, "adn_channel_sum: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_channel_sum: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_channel_sum", dtype);
   const int64_t need = adn_channel_sum_workspace_bytes(rows, C);
   ADN_CHECK_ARG(workspace && workspace_bytes >= need, "adn_channel_sum: workspace too small");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -448,9 +450,13 @@ extern "C" int adn_channel_sum(const void* x, int64_t rows, int32_t C, int32_t l
   float* part = reinterpret_cast<float*>(workspace);
   const bool vec = (C & 7) == 0 && (ld & 7) == 0;
   const dim3 grid(P, (unsigned)adn_cdiv(C, vec ? 2048 : 256));
-  if (dtype == ADN_BF16) hipLaunchKernelGGL((channel_sum_partial<uint16_t>), grid, dim3(256), 0, st, x, rows, C, ld, part);
-  else hipLaunchKernelGGL((channel_sum_partial<float>), grid, dim3(256), 0, st, x, rows, C, ld, part);
-  ADN_CHECK_LAUNCH();
+  const int rc = adn_by_dtype("adn_channel_sum", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((channel_sum_partial<T>), grid, dim3(256), 0, st, x, rows, C, ld, part);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
+  if (rc != ADN_OK) return rc;
   hipLaunchKernelGGL(channel_sum_final, dim3((unsigned)adn_cdiv(C, 4)), dim3(256), 0, st, part, P, C, out);
   ADN_CHECK_LAUNCH();
   return ADN_OK;
@@ -460,16 +466,20 @@ extern "C" int adn_gate_bwd(void* t, const void* att, int64_t n, int32_t dtype, 
                             const float* bias, int32_t C, float* dgamma, float* dbias, float* dw, int64_t nw,
                             void* workspace, int64_t workspace_bytes, void* stream) {
   ADN_CHECK_ARG(t && att && gamma && gsum && dgamma && n > 0 && C > 0 && nw >= 0, "adn_gate_bwd: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_gate_bwd: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_gate_bwd", dtype);
   ADN_CHECK_ARG(workspace && workspace_bytes >= 1024 * 8, "adn_gate_bwd: workspace too small (needs 8 KiB)");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   int64_t nb = adn_cdiv(n, 256 * 8);
   if (nb > 1024) nb = 1024;
   if (nb < 1) nb = 1;
   double* part = reinterpret_cast<double*>(workspace);
-  if (dtype == ADN_BF16) hipLaunchKernelGGL((gate_bwd_kernel<uint16_t>), dim3((unsigned)nb), dim3(256), 0, st, t, att, n, gamma, part);
-  else hipLaunchKernelGGL((gate_bwd_kernel<float>), dim3((unsigned)nb), dim3(256), 0, st, t, att, n, gamma, part);
-  ADN_CHECK_LAUNCH();
+  const int rc = adn_by_dtype("adn_gate_bwd", dtype, [&](auto tt) {
+    using T = decltype(tt);
+    hipLaunchKernelGGL((gate_bwd_kernel<T>), dim3((unsigned)nb), dim3(256), 0, st, t, att, n, gamma, part);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
+  if (rc != ADN_OK) return rc;
   int64_t fb = adn_cdiv(nw, 256);
   if (fb > 1024) fb = 1024;
   if (fb < 1) fb = 1;

@@ -214,7 +214,7 @@ extern "C" int64_t adn_coarse_loss_workspace_bytes(int64_t pixels) {
 
 extern "C" int adn_coarse_loss(const AdnCoarseLoss* d, void* stream) {
   ADN_CHECK_ARG(d && d->logits && d->centers && d->depth && d->pixels > 0, "adn_coarse_loss: null operand or no pixels");
-  ADN_CHECK_ARG(d->dtype == ADN_F32 || d->dtype == ADN_BF16, "adn_coarse_loss: bad dtype %d", d->dtype);
+  ADN_CHECK_DTYPE("adn_coarse_loss", d->dtype);
   ADN_CHECK_ARG(d->nb >= 2 && d->nb <= kMaxNb, "adn_coarse_loss: n_bins %d outside the supported range [2, %d]", d->nb, kMaxNb);
   ADN_CHECK_ARG(d->ld >= d->nb, "adn_coarse_loss: row stride %d < n_bins %d", d->ld, d->nb);
   ADN_CHECK_ARG(!d->dlogits || d->bins, "adn_coarse_loss: a gradient needs the target bins");
@@ -234,9 +234,10 @@ extern "C" int adn_coarse_loss(const AdnCoarseLoss* d, void* stream) {
   p.ce_coef = d->bins ? (float)((double)d->ce_weight / (double)d->pixels_global) : 0.f;
   p.reg_weight = d->reg_weight;
   const dim3 grid(loss_blocks(d->pixels));
-  launch_bin_rows(d->dtype, d->nb, d->ld, d->logits, d->dlogits, [&](auto row) {
+  const int rc = launch_bin_rows("adn_coarse_loss", d->dtype, d->nb, d->ld, d->logits, d->dlogits, [&](auto row) {
     hipLaunchKernelGGL((coarse_loss_kernel<typename decltype(row)::type>), grid, dim3(256), 0, st, p);
   });
+  if (rc != ADN_OK) return rc;
   ADN_CHECK_LAUNCH();
   return ADN_OK;
 }

@@ -161,7 +161,7 @@ inline int eval_blocks(int64_t pixels) { return adn_grid_blocks(pixels, 1024, kL
 extern "C" int adn_coarse_decode(const AdnCoarseDecode* d, void* stream) {
   ADN_CHECK_ARG(d, "adn_coarse_decode: null descriptor");
   ADN_CHECK_ARG(d->logits && d->centers && d->pixels > 0, "adn_coarse_decode: null operand or no pixels");
-  ADN_CHECK_ARG(d->dtype == ADN_F32 || d->dtype == ADN_BF16, "adn_coarse_decode: bad dtype %d", d->dtype);
+  ADN_CHECK_DTYPE("adn_coarse_decode", d->dtype);
   ADN_CHECK_ARG(d->nb >= 2 && d->nb <= kMaxNb, "adn_coarse_decode: n_bins %d outside the supported range [2, %d]", d->nb, kMaxNb);
   ADN_CHECK_ARG(d->ld >= d->nb, "adn_coarse_decode: row stride %d < n_bins %d", d->ld, d->nb);
   ADN_CHECK_ARG(d->mean || d->hard || d->stdev || d->entropy || d->confidence || d->argmax,
@@ -173,9 +173,10 @@ extern "C" int adn_coarse_decode(const AdnCoarseDecode* d, void* stream) {
   p.argmax = d->argmax;
   p.pixels = d->pixels; p.nb = d->nb; p.ld = d->ld;
   const dim3 grid(decode_blocks(d->pixels));
-  launch_bin_rows(d->dtype, d->nb, d->ld, d->logits, nullptr, [&](auto row) {
+  const int rc = launch_bin_rows("adn_coarse_decode", d->dtype, d->nb, d->ld, d->logits, nullptr, [&](auto row) {
     hipLaunchKernelGGL((coarse_decode_kernel<typename decltype(row)::type>), grid, dim3(256), 0, st, p);
   });
+  if (rc != ADN_OK) return rc;
   ADN_CHECK_LAUNCH();
   return ADN_OK;
 }

@@ -273,7 +273,7 @@ extern "C" int adn_convt_n1_forward_ex(int32_t dtype, int32_t B, int32_t Hs, int
                                        const void* in1, int32_t C1, const float* w, const float* bias,
                                        int32_t final_act, float* out, void* workspace, int64_t workspace_bytes,
                                        int32_t flags, void* stream) {
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_convt_n1_forward: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_convt_n1_forward", dtype);
   ADN_CHECK_ARG(B > 0 && Hs > 0 && Ws > 0 && C0 > 0 && C1 >= 0, "adn_convt_n1_forward: bad shape");
   ADN_CHECK_ARG(in0 && (C1 == 0 || in1) && w && out && workspace, "adn_convt_n1_forward: null operand");
   ADN_CHECK_ARG((flags & ~(ADN_N1_RELU_IN0 | ADN_N1_TWO_LAUNCH)) == 0, "adn_convt_n1_forward: bad flags %d", flags);
@@ -287,11 +287,11 @@ extern "C" int adn_convt_n1_forward_ex(int32_t dtype, int32_t B, int32_t Hs, int
   float* P = reinterpret_cast<float*>(workspace);
   const bool two = (flags & ADN_N1_TWO_LAUNCH) != 0;
   const bool relu0 = (flags & ADN_N1_RELU_IN0) != 0;
-  if (dtype == ADN_BF16)
-    return relu0 ? launch_n1<uint16_t, true>(B, Hs, Ws, in0, C0, in1, C1, w, bias, final_act, out, P, two, st)
-                 : launch_n1<uint16_t, false>(B, Hs, Ws, in0, C0, in1, C1, w, bias, final_act, out, P, two, st);
-  return relu0 ? launch_n1<float, true>(B, Hs, Ws, in0, C0, in1, C1, w, bias, final_act, out, P, two, st)
-               : launch_n1<float, false>(B, Hs, Ws, in0, C0, in1, C1, w, bias, final_act, out, P, two, st);
+  return adn_by_dtype("adn_convt_n1_forward", dtype, [&](auto t) {
+    using T = decltype(t);
+    return relu0 ? launch_n1<T, true>(B, Hs, Ws, in0, C0, in1, C1, w, bias, final_act, out, P, two, st)
+                 : launch_n1<T, false>(B, Hs, Ws, in0, C0, in1, C1, w, bias, final_act, out, P, two, st);
+  });
 }
 
 extern "C" int adn_convt_n1_forward(int32_t dtype, int32_t B, int32_t Hs, int32_t Ws, const void* in0, int32_t C0,

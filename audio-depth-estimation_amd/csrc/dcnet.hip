@@ -627,42 +627,35 @@ inline int next_pow2(int v) {
 
 }  // namespace
 
-#define ADN_DISPATCH_V(KERNEL, TYPE, grid, st, ...)                                              \
-  do {                                                                                           \
-    if ((C & 7) == 0) hipLaunchKernelGGL((KERNEL<TYPE, 8>), grid, dim3(256), 0, st, __VA_ARGS__); \
-    else hipLaunchKernelGGL((KERNEL<TYPE, 1>), grid, dim3(256), 0, st, __VA_ARGS__);              \
-  } while (0)
-
-extern "C" int adn_maxpool2_fwd(const void* src, void* dst, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype,
-                                void* stream) {
-  ADN_CHECK_ARG(src && dst && B > 0 && H > 1 && W > 1 && C > 0, "adn_maxpool2_fwd: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_maxpool2_fwd: bad dtype %d", dtype);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int64_t work = (int64_t)B * (H / 2) * (W / 2) * ((C & 7) == 0 ? C / 8 : C);
-  if (dtype == ADN_BF16) {
-    auto s = reinterpret_cast<const uint16_t*>(src);
-    auto d = reinterpret_cast<uint16_t*>(dst);
-    ADN_DISPATCH_V(maxpool2_fwd_kernel, uint16_t, dim3(blocks_for(work)), st, s, d, B, H, W, C);
-  } else {
-    auto s = reinterpret_cast<const float*>(src);
-    auto d = reinterpret_cast<float*>(dst);
-    ADN_DISPATCH_V(maxpool2_fwd_kernel, float, dim3(blocks_for(work)), st, s, d, B, H, W, C);
-  }
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
-}
-
-// bf16 forward kernels that also write the MX-fp8 copy of their output (C % 32 == 0), for the fp8 conv path
+// bf16 forward kernels that also write the MX-fp8 copy of their output (C % 32 == 0), for the fp8 conv path.
+// (adn_maxpool2_fwd_mx8 stands ahead of adn_maxpool2_fwd on purpose: kernels are emitted in the order in which they
+// are first named, and this keeps <bf16, 8> first in the code object, where it was before the dispatcher.)
 extern "C" int adn_maxpool2_fwd_mx8(const void* src, void* dst, int32_t B, int32_t H, int32_t W, int32_t C, void* out8,
                                     void* out_scales, void* stream) {
   ADN_CHECK_ARG(src && dst && out8 && out_scales && B > 0 && H > 1 && W > 1 && C > 0 && C % 32 == 0,
                 "adn_maxpool2_fwd_mx8: bad arguments (C=%d must be a multiple of 32)", C);
   const int64_t work = (int64_t)B * (H / 2) * (W / 2) * (C / 8);
   hipLaunchKernelGGL((maxpool2_fwd_kernel<uint16_t, 8>), dim3(blocks_for(work)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     reinterpret_cast<const uint16_t*>(src), reinterpret_cast<uint16_t*>(dst), B, H, W, C,
-                     reinterpret_cast<uint2*>(out8), reinterpret_cast<uint8_t*>(out_scales));
+                     adn_as<uint16_t>(src), adn_as<uint16_t>(dst), B, H, W, C, adn_as<uint2>(out8),
+                     adn_as<uint8_t>(out_scales));
   ADN_CHECK_LAUNCH();
   return ADN_OK;
+}
+
+extern "C" int adn_maxpool2_fwd(const void* src, void* dst, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype,
+                                void* stream) {
+  ADN_CHECK_ARG(src && dst && B > 0 && H > 1 && W > 1 && C > 0, "adn_maxpool2_fwd: bad arguments");
+  ADN_CHECK_DTYPE("adn_maxpool2_fwd", dtype);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t work = (int64_t)B * (H / 2) * (W / 2) * ((C & 7) == 0 ? C / 8 : C);
+  return adn_by_dtype_v("adn_maxpool2_fwd", dtype, (C & 7) == 0, [&](auto t, auto v) {
+    using T = decltype(t);
+    constexpr int V = decltype(v)::value;
+    hipLaunchKernelGGL((maxpool2_fwd_kernel<T, V>), dim3(blocks_for(work)), dim3(256), 0, st, adn_as<T>(src),
+                       adn_as<T>(dst), B, H, W, C);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int adn_upsample2x_fwd_mx8(const void* src, void* dst, int32_t B, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
@@ -673,9 +666,8 @@ extern "C" int adn_upsample2x_fwd_mx8(const void* src, void* dst, int32_t B, int
   const int padT = (Ho - 2 * Hi) / 2, padL = (Wo - 2 * Wi) / 2;
   const int64_t work = (int64_t)B * Ho * Wo * (C / 8);
   hipLaunchKernelGGL((upsample2x_fwd_kernel<uint16_t, 8>), dim3(blocks_for(work)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const uint16_t*>(src),
-                     reinterpret_cast<uint16_t*>(dst), B, Hi, Wi, Ho, Wo, padT, padL, C, reinterpret_cast<uint2*>(out8),
-                     reinterpret_cast<uint8_t*>(out_scales));
+                     reinterpret_cast<hipStream_t>(stream), adn_as<uint16_t>(src), adn_as<uint16_t>(dst), B, Hi, Wi, Ho,
+                     Wo, padT, padL, C, adn_as<uint2>(out8), adn_as<uint8_t>(out_scales));
   ADN_CHECK_LAUNCH();
   return ADN_OK;
 }
@@ -693,22 +685,19 @@ extern "C" int adn_maxpool2_bwd_tail(const void* gdst, const void* y, void* gsrc
                                      int32_t accumulate, int32_t dtype, const void* z, const float* mean, const float* istd,
                                      float* partials, void* stream) {
   ADN_CHECK_ARG(gdst && y && gsrc && z && mean && istd && partials && B > 0 && H > 1 && W > 1, "adn_maxpool2_bwd_tail: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_maxpool2_bwd_tail: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_maxpool2_bwd_tail", dtype);
   const int64_t work = (int64_t)B * ((H + 1) / 2) * ((W + 1) / 2) * (C / 8);
   const int64_t blocks = adn_tail_stats_blocks(work, C);
   ADN_CHECK_ARG(blocks > 0, "adn_maxpool2_bwd_tail: C=%d not supported", C);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   TailStats ts{y, z, mean, istd, partials};
-  if (dtype == ADN_BF16)
-    hipLaunchKernelGGL((maxpool2_bwd_kernel<uint16_t, 8>), dim3((unsigned)blocks), dim3(256), 0, st,
-                       reinterpret_cast<const uint16_t*>(gdst), reinterpret_cast<const uint16_t*>(y),
-                       reinterpret_cast<uint16_t*>(gsrc), B, H, W, C, accumulate, ts);
-  else
-    hipLaunchKernelGGL((maxpool2_bwd_kernel<float, 8>), dim3((unsigned)blocks), dim3(256), 0, st,
-                       reinterpret_cast<const float*>(gdst), reinterpret_cast<const float*>(y), reinterpret_cast<float*>(gsrc), B,
-                       H, W, C, accumulate, ts);
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype("adn_maxpool2_bwd_tail", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((maxpool2_bwd_kernel<T, 8>), dim3((unsigned)blocks), dim3(256), 0, st, adn_as<T>(gdst),
+                       adn_as<T>(y), adn_as<T>(gsrc), B, H, W, C, accumulate, ts);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int adn_upsample2x_bwd_tail(const void* gdst, void* gsrc, int32_t B, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
@@ -716,44 +705,36 @@ extern "C" int adn_upsample2x_bwd_tail(const void* gdst, void* gsrc, int32_t B, 
                                        const float* mean, const float* istd, float* partials, void* stream) {
   ADN_CHECK_ARG(gdst && gsrc && y && z && mean && istd && partials && B > 0 && Hi > 0 && Wi > 0, "adn_upsample2x_bwd_tail: bad arguments");
   ADN_CHECK_ARG(Ho >= 2 * Hi && Wo >= 2 * Wi, "adn_upsample2x_bwd_tail: target %dx%d smaller than 2x source %dx%d", Ho, Wo, Hi, Wi);
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_upsample2x_bwd_tail: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_upsample2x_bwd_tail", dtype);
   const int padT = (Ho - 2 * Hi) / 2, padL = (Wo - 2 * Wi) / 2;
   const int64_t work = (int64_t)B * Hi * Wi * (C / 8);
   const int64_t blocks = adn_tail_stats_blocks(work, C);
   ADN_CHECK_ARG(blocks > 0, "adn_upsample2x_bwd_tail: C=%d not supported", C);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   TailStats ts{y, z, mean, istd, partials};
-  if (dtype == ADN_BF16)
-    hipLaunchKernelGGL((upsample2x_bwd_kernel<uint16_t, 8>), dim3((unsigned)blocks), dim3(256), 0, st,
-                       reinterpret_cast<const uint16_t*>(gdst), reinterpret_cast<uint16_t*>(gsrc), B, Hi, Wi, Ho, Wo, padT, padL, C,
-                       accumulate, ts);
-  else
-    hipLaunchKernelGGL((upsample2x_bwd_kernel<float, 8>), dim3((unsigned)blocks), dim3(256), 0, st,
-                       reinterpret_cast<const float*>(gdst), reinterpret_cast<float*>(gsrc), B, Hi, Wi, Ho, Wo, padT, padL, C,
-                       accumulate, ts);
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype("adn_upsample2x_bwd_tail", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((upsample2x_bwd_kernel<T, 8>), dim3((unsigned)blocks), dim3(256), 0, st, adn_as<T>(gdst),
+                       adn_as<T>(gsrc), B, Hi, Wi, Ho, Wo, padT, padL, C, accumulate, ts);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int adn_maxpool2_bwd(const void* gdst, const void* y, void* gsrc, int32_t B, int32_t H, int32_t W,
                                 int32_t C, int32_t accumulate, int32_t dtype, void* stream) {
   ADN_CHECK_ARG(gdst && y && gsrc && B > 0 && H > 1 && W > 1 && C > 0, "adn_maxpool2_bwd: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_maxpool2_bwd: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_maxpool2_bwd", dtype);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t work = (int64_t)B * ((H + 1) / 2) * ((W + 1) / 2) * ((C & 7) == 0 ? C / 8 : C);
-  if (dtype == ADN_BF16) {
-    auto gd = reinterpret_cast<const uint16_t*>(gdst);
-    auto yy = reinterpret_cast<const uint16_t*>(y);
-    auto gs = reinterpret_cast<uint16_t*>(gsrc);
-    ADN_DISPATCH_V(maxpool2_bwd_kernel, uint16_t, dim3(blocks_for(work)), st, gd, yy, gs, B, H, W, C, accumulate);
-  } else {
-    auto gd = reinterpret_cast<const float*>(gdst);
-    auto yy = reinterpret_cast<const float*>(y);
-    auto gs = reinterpret_cast<float*>(gsrc);
-    ADN_DISPATCH_V(maxpool2_bwd_kernel, float, dim3(blocks_for(work)), st, gd, yy, gs, B, H, W, C, accumulate);
-  }
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype_v("adn_maxpool2_bwd", dtype, (C & 7) == 0, [&](auto t, auto v) {
+    using T = decltype(t);
+    constexpr int V = decltype(v)::value;
+    hipLaunchKernelGGL((maxpool2_bwd_kernel<T, V>), dim3(blocks_for(work)), dim3(256), 0, st, adn_as<T>(gdst),
+                       adn_as<T>(y), adn_as<T>(gsrc), B, H, W, C, accumulate);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int adn_upsample2x_fwd(const void* src, void* dst, int32_t B, int32_t Hi, int32_t Wi, int32_t Ho,
@@ -761,21 +742,18 @@ extern "C" int adn_upsample2x_fwd(const void* src, void* dst, int32_t B, int32_t
   ADN_CHECK_ARG(src && dst && B > 0 && Hi > 0 && Wi > 0 && C > 0, "adn_upsample2x_fwd: bad arguments");
   ADN_CHECK_ARG(Ho >= 2 * Hi && Wo >= 2 * Wi, "adn_upsample2x_fwd: target %dx%d smaller than 2x source %dx%d", Ho, Wo,
                 Hi, Wi);
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_upsample2x_fwd: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_upsample2x_fwd", dtype);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int padT = (Ho - 2 * Hi) / 2, padL = (Wo - 2 * Wi) / 2;      // F.pad(diff // 2, diff - diff // 2)
   const int64_t work = (int64_t)B * Ho * Wo * ((C & 7) == 0 ? C / 8 : C);
-  if (dtype == ADN_BF16) {
-    auto s = reinterpret_cast<const uint16_t*>(src);
-    auto d = reinterpret_cast<uint16_t*>(dst);
-    ADN_DISPATCH_V(upsample2x_fwd_kernel, uint16_t, dim3(blocks_for(work)), st, s, d, B, Hi, Wi, Ho, Wo, padT, padL, C);
-  } else {
-    auto s = reinterpret_cast<const float*>(src);
-    auto d = reinterpret_cast<float*>(dst);
-    ADN_DISPATCH_V(upsample2x_fwd_kernel, float, dim3(blocks_for(work)), st, s, d, B, Hi, Wi, Ho, Wo, padT, padL, C);
-  }
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype_v("adn_upsample2x_fwd", dtype, (C & 7) == 0, [&](auto t, auto v) {
+    using T = decltype(t);
+    constexpr int V = decltype(v)::value;
+    hipLaunchKernelGGL((upsample2x_fwd_kernel<T, V>), dim3(blocks_for(work)), dim3(256), 0, st, adn_as<T>(src),
+                       adn_as<T>(dst), B, Hi, Wi, Ho, Wo, padT, padL, C);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int adn_upsample2x_bwd(const void* gdst, void* gsrc, int32_t B, int32_t Hi, int32_t Wi, int32_t Ho,
@@ -783,42 +761,34 @@ extern "C" int adn_upsample2x_bwd(const void* gdst, void* gsrc, int32_t B, int32
   ADN_CHECK_ARG(gdst && gsrc && B > 0 && Hi > 0 && Wi > 0 && C > 0, "adn_upsample2x_bwd: bad arguments");
   ADN_CHECK_ARG(Ho >= 2 * Hi && Wo >= 2 * Wi, "adn_upsample2x_bwd: target %dx%d smaller than 2x source %dx%d", Ho, Wo,
                 Hi, Wi);
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_upsample2x_bwd: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_upsample2x_bwd", dtype);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int padT = (Ho - 2 * Hi) / 2, padL = (Wo - 2 * Wi) / 2;
   const int64_t work = (int64_t)B * Hi * Wi * ((C & 7) == 0 ? C / 8 : C);
-  if (dtype == ADN_BF16) {
-    auto gd = reinterpret_cast<const uint16_t*>(gdst);
-    auto gs = reinterpret_cast<uint16_t*>(gsrc);
-    ADN_DISPATCH_V(upsample2x_bwd_kernel, uint16_t, dim3(blocks_for(work)), st, gd, gs, B, Hi, Wi, Ho, Wo, padT, padL, C,
-                    accumulate);
-  } else {
-    auto gd = reinterpret_cast<const float*>(gdst);
-    auto gs = reinterpret_cast<float*>(gsrc);
-    ADN_DISPATCH_V(upsample2x_bwd_kernel, float, dim3(blocks_for(work)), st, gd, gs, B, Hi, Wi, Ho, Wo, padT, padL, C,
-                    accumulate);
-  }
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype_v("adn_upsample2x_bwd", dtype, (C & 7) == 0, [&](auto t, auto v) {
+    using T = decltype(t);
+    constexpr int V = decltype(v)::value;
+    hipLaunchKernelGGL((upsample2x_bwd_kernel<T, V>), dim3(blocks_for(work)), dim3(256), 0, st, adn_as<T>(gdst),
+                       adn_as<T>(gsrc), B, Hi, Wi, Ho, Wo, padT, padL, C, accumulate);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int adn_pixel_shuffle2(const void* src, void* dst, int32_t B, int32_t H, int32_t W, int32_t C, int32_t inverse,
                                   int32_t dtype, void* stream) {
   ADN_CHECK_ARG(src && dst && B > 0 && H > 0 && W > 0 && C > 0, "adn_pixel_shuffle2: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_pixel_shuffle2: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_pixel_shuffle2", dtype);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t work = (int64_t)B * H * W * 4 * ((C & 7) == 0 ? C / 8 : C);
-  if (dtype == ADN_BF16) {
-    auto sp = reinterpret_cast<const uint16_t*>(src);
-    auto dp = reinterpret_cast<uint16_t*>(dst);
-    ADN_DISPATCH_V(pixel_shuffle2_kernel, uint16_t, dim3(blocks_for(work)), st, sp, dp, B, H, W, C, inverse);
-  } else {
-    auto sp = reinterpret_cast<const float*>(src);
-    auto dp = reinterpret_cast<float*>(dst);
-    ADN_DISPATCH_V(pixel_shuffle2_kernel, float, dim3(blocks_for(work)), st, sp, dp, B, H, W, C, inverse);
-  }
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype_v("adn_pixel_shuffle2", dtype, (C & 7) == 0, [&](auto t, auto v) {
+    using T = decltype(t);
+    constexpr int V = decltype(v)::value;
+    hipLaunchKernelGGL((pixel_shuffle2_kernel<T, V>), dim3(blocks_for(work)), dim3(256), 0, st, adn_as<T>(src),
+                       adn_as<T>(dst), B, H, W, C, inverse);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int adn_clamp_range(const float* x, const float* g, int64_t n, float max_depth, float* out, void* stream) {
@@ -839,19 +809,16 @@ extern "C" int64_t adn_relu_bwd_stats_num_partials(int64_t pixels, int32_t C) {
 extern "C" int adn_relu_bwd_stats(void* g, const void* y, const void* z, const float* mean, const float* istd,
                                   int64_t pixels, int32_t C, int32_t dtype, float* partials, void* stream) {
   ADN_CHECK_ARG(g && y && z && mean && istd && partials && pixels > 0 && C > 0, "adn_relu_bwd_stats: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_relu_bwd_stats: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_relu_bwd_stats", dtype);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const unsigned P = (unsigned)adn_relu_bwd_stats_num_partials(pixels, C);
-  if (dtype == ADN_BF16)
-    hipLaunchKernelGGL((relu_bwd_stats_kernel<uint16_t>), dim3(P), dim3(256), 0, st, reinterpret_cast<uint16_t*>(g),
-                       reinterpret_cast<const uint16_t*>(y), reinterpret_cast<const uint16_t*>(z), mean, istd, pixels,
-                       C, partials);
-  else
-    hipLaunchKernelGGL((relu_bwd_stats_kernel<float>), dim3(P), dim3(256), 0, st, reinterpret_cast<float*>(g),
-                       reinterpret_cast<const float*>(y), reinterpret_cast<const float*>(z), mean, istd, pixels, C,
-                       partials);
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype("adn_relu_bwd_stats", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((relu_bwd_stats_kernel<T>), dim3(P), dim3(256), 0, st, adn_as<T>(g), adn_as<T>(y), adn_as<T>(z),
+                       mean, istd, pixels, C, partials);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 static int head_lpp(int C, int V) {
@@ -863,21 +830,19 @@ static int head_lpp(int C, int V) {
 extern "C" int adn_head1x1_fwd(const void* x, const float* w, const float* bias, int64_t pixels, int32_t C,
                                int32_t dtype, int32_t act, float max_depth, float* zpre, float* out, void* stream) {
   ADN_CHECK_ARG(x && w && zpre && out && pixels > 0 && C > 0, "adn_head1x1_fwd: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_head1x1_fwd: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_head1x1_fwd", dtype);
   ADN_CHECK_ARG(act >= 0 && act <= 3, "adn_head1x1_fwd: bad act %d", act);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int V = (C & 7) == 0 ? 8 : 1;
   const int lpp = head_lpp(C, V);
   const dim3 grid(blocks_for(pixels, 256 / lpp));
-  if (dtype == ADN_BF16) {
-    auto xx = reinterpret_cast<const uint16_t*>(x);
-    ADN_DISPATCH_V(head1x1_fwd_kernel, uint16_t, grid, st, xx, w, bias, pixels, C, lpp, act, max_depth, zpre, out);
-  } else {
-    auto xx = reinterpret_cast<const float*>(x);
-    ADN_DISPATCH_V(head1x1_fwd_kernel, float, grid, st, xx, w, bias, pixels, C, lpp, act, max_depth, zpre, out);
-  }
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype_v("adn_head1x1_fwd", dtype, V == 8, [&](auto t, auto v) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((head1x1_fwd_kernel<T, decltype(v)::value>), grid, dim3(256), 0, st, adn_as<T>(x), w, bias, pixels, C, lpp, act,
+                       max_depth, zpre, out);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int64_t adn_head1x1_bwd_workspace_bytes(int64_t pixels, int32_t C) {
@@ -893,7 +858,7 @@ extern "C" int adn_head1x1_bwd(const float* gout, const float* zpre, const void*
                                int32_t C, int32_t dtype, int32_t act, float max_depth, void* gx, float* dw, float* db,
                                void* workspace, int64_t workspace_bytes, void* stream) {
   ADN_CHECK_ARG(gout && zpre && x && w && gx && dw && pixels > 0 && C > 0, "adn_head1x1_bwd: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_head1x1_bwd: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_head1x1_bwd", dtype);
   ADN_CHECK_ARG(act >= 0 && act <= 3, "adn_head1x1_bwd: bad act %d", act);
   const int V = (C & 7) == 0 ? 8 : 1;
   const int lpp = head_lpp(C, V);
@@ -904,16 +869,14 @@ extern "C" int adn_head1x1_bwd(const float* gout, const float* zpre, const void*
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const unsigned nb = (unsigned)(need / ((C + 1) * sizeof(float)));
   float* partials = reinterpret_cast<float*>(workspace);
-  if (dtype == ADN_BF16) {
-    auto xx = reinterpret_cast<const uint16_t*>(x);
-    auto gg = reinterpret_cast<uint16_t*>(gx);
-    ADN_DISPATCH_V(head1x1_bwd_kernel, uint16_t, dim3(nb), st, gout, zpre, xx, w, pixels, C, lpp, act, max_depth, gg, partials);
-  } else {
-    auto xx = reinterpret_cast<const float*>(x);
-    auto gg = reinterpret_cast<float*>(gx);
-    ADN_DISPATCH_V(head1x1_bwd_kernel, float, dim3(nb), st, gout, zpre, xx, w, pixels, C, lpp, act, max_depth, gg, partials);
-  }
-  ADN_CHECK_LAUNCH();
+  const int rc = adn_by_dtype_v("adn_head1x1_bwd", dtype, V == 8, [&](auto t, auto v) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((head1x1_bwd_kernel<T, decltype(v)::value>), dim3(nb), dim3(256), 0, st, gout, zpre, adn_as<T>(x), w, pixels, C, lpp,
+                       act, max_depth, adn_as<T>(gx), partials);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
+  if (rc != ADN_OK) return rc;
   hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)adn_cdiv(C + 1, 4)), dim3(256), 0, st, partials, (int64_t)nb, C + 1,
                      dw, C, db);
   ADN_CHECK_LAUNCH();

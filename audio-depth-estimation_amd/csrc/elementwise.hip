@@ -239,6 +239,7 @@ __global__ __launch_bounds__(256) void bn_fwd_finalize_kernel(const float* parti
   int c;
   double s1, s2;
   if (bn_partial_sums<WIDE>(partials, P, C, c, s1, s2)) {
+    // (statistics step: the same lines stand in bn_fwd_fused_kernel -- change both.  A shared helper changed the kernel.)
     const double mu = s1 / count;
     double var = s2 / count - mu * mu;
     if (var < 0.0) var = 0.0;
@@ -302,6 +303,7 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const T* z, int64_t pixels,
       }
       float v[8], o[8];
       load8<T>(z, e, v);
+      // (forward apply: the same body stands in bn_fwd_fused_kernel -- change both.  A shared helper changed the kernel.)
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] = v[k] * sc[k] + sh[k];
       if (out_leaky) {
@@ -347,6 +349,13 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* parti
   }
 }
 
+// g <- scale * (g - mean(g) - xhat * mean(g xhat)), xhat = (z - mean) * istd: the 8-wide body of bn_bwd_apply_kernel and
+// bn_bwd_fused_kernel.  Scalars by value: the arrays stay in the kernels, so their device code is what it was.
+__device__ __forceinline__ float bn_bwd_apply1(float g, float z, float scale, float mean, float istd, float c0, float c1) {
+  const float xh = (z - mean) * istd;
+  return scale * (g - c0 - xh * c1);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(T* g, const T* z, int64_t pixels, int C,
                                                            const float* scale, const float* mean, const float* istd,
@@ -382,10 +391,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(T* g, const T* z, int
       load8<T>(g, e, gv);
       load8<T>(z, e, zv);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float xh = (zv[k] - cm[k]) * ci[k];
-        gv[k] = cs[k] * (gv[k] - c0[k] - xh * c1[k]);
-      }
+      for (int k = 0; k < 8; ++k) gv[k] = bn_bwd_apply1(gv[k], zv[k], cs[k], cm[k], ci[k], c0[k], c1[k]);
       store8<T>(g, e, gv);
       if constexpr (sizeof(T) == 2) {
         if (q8) {
@@ -460,6 +466,7 @@ __global__ __launch_bounds__(256) void bn_fwd_fused_kernel(const float* partials
   bn_block_sums(partials, P, C, c0, sh, s1, s2);
   if (threadIdx.x < 32) {
     const int c = c0 + threadIdx.x;
+    // (statistics step: twin of bn_fwd_finalize_kernel -- change both)
     const double mu = s1 / count;
     double var = s2 / count - mu * mu;
     if (var < 0.0) var = 0.0;
@@ -493,6 +500,7 @@ __global__ __launch_bounds__(256) void bn_fwd_fused_kernel(const float* partials
     const int64_t e = r * C + c0 + chunk * 8;
     float v[8], o[8];
     load8<T>(z, e, v);
+    // (forward apply: twin of the 8-wide body of bn_act_kernel -- change both)
 #pragma unroll
     for (int k = 0; k < 8; ++k) v[k] = v[k] * sc[k] + shf[k];
     if (out_leaky) {
@@ -547,10 +555,7 @@ __global__ __launch_bounds__(256) void bn_bwd_fused_kernel(const float* partials
     load8<T>(g, e, gv);
     load8<T>(z, e, zv);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float xh = (zv[k] - k1[k]) * k2[k];
-      gv[k] = k0[k] * (gv[k] - k3[k] - xh * k4[k]);
-    }
+    for (int k = 0; k < 8; ++k) gv[k] = bn_bwd_apply1(gv[k], zv[k], k0[k], k1[k], k2[k], k3[k], k4[k]);
     store8<T>(g, e, gv);
   }
 }
@@ -560,28 +565,28 @@ __global__ __launch_bounds__(256) void bn_bwd_fused_kernel(const float* partials
 extern "C" int adn_pack_weights(const float* master, int32_t X, int32_t Y, int32_t y_pad, int32_t dtype,
                                 void* s2_out, void* t2_out, void* stream) {
   ADN_CHECK_ARG(master && X > 0 && Y > 0 && y_pad >= Y, "adn_pack_weights: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_pack_weights: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_pack_weights", dtype);
   ADN_CHECK_ARG(s2_out || t2_out, "adn_pack_weights: no output");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t n = (int64_t)X * 16 * y_pad;
   if (s2_out) {
-    if (dtype == ADN_BF16)
-      hipLaunchKernelGGL((pack_s2_kernel<uint16_t>), dim3(blocks_for(n)), dim3(256), 0, st, master, X, Y, y_pad,
-                         reinterpret_cast<uint16_t*>(s2_out));
-    else
-      hipLaunchKernelGGL((pack_s2_kernel<float>), dim3(blocks_for(n)), dim3(256), 0, st, master, X, Y, y_pad,
-                         reinterpret_cast<float*>(s2_out));
-    ADN_CHECK_LAUNCH();
+    const int rc = adn_by_dtype("adn_pack_weights", dtype, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((pack_s2_kernel<T>), dim3(blocks_for(n)), dim3(256), 0, st, master, X, Y, y_pad,
+                         adn_as<T>(s2_out));
+      ADN_CHECK_LAUNCH();
+      return ADN_OK;
+    });
+    if (rc != ADN_OK) return rc;
   }
   if (t2_out) {
     const dim3 grid((unsigned)(adn_cdiv(X, 32) * adn_cdiv(Y, 32)), 16);
-    if (dtype == ADN_BF16)
-      hipLaunchKernelGGL((pack_t2_kernel<uint16_t>), grid, dim3(256), 0, st, master, X, Y,
-                         reinterpret_cast<uint16_t*>(t2_out));
-    else
-      hipLaunchKernelGGL((pack_t2_kernel<float>), grid, dim3(256), 0, st, master, X, Y,
-                         reinterpret_cast<float*>(t2_out));
-    ADN_CHECK_LAUNCH();
+    return adn_by_dtype("adn_pack_weights", dtype, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((pack_t2_kernel<T>), grid, dim3(256), 0, st, master, X, Y, adn_as<T>(t2_out));
+      ADN_CHECK_LAUNCH();
+      return ADN_OK;
+    });
   }
   return ADN_OK;
 }
@@ -590,18 +595,17 @@ extern "C" int adn_nchw_slice_to_nhwc(const float* src, void* dst, int32_t B, in
                                       int32_t c_pad, int32_t H, int32_t W, int32_t dtype, void* stream) {
   ADN_CHECK_ARG(src && dst && B > 0 && C > 0 && c_pad >= C && H > 0 && W > 0 && c_lo >= 0 && c_lo + C <= C_total,
                 "adn_nchw_slice_to_nhwc: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_nchw_slice_to_nhwc: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_nchw_slice_to_nhwc", dtype);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t n = (int64_t)B * H * W;
   const float* s0 = src + (int64_t)c_lo * H * W;
-  if (dtype == ADN_BF16)
-    hipLaunchKernelGGL((nchw_to_nhwc_kernel<uint16_t>), dim3(blocks_for(n)), dim3(256), 0, st, s0,
-                       reinterpret_cast<uint16_t*>(dst), B, C, c_pad, (int64_t)H * W, (int64_t)C_total);
-  else
-    hipLaunchKernelGGL((nchw_to_nhwc_kernel<float>), dim3(blocks_for(n)), dim3(256), 0, st, s0,
-                       reinterpret_cast<float*>(dst), B, C, c_pad, (int64_t)H * W, (int64_t)C_total);
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype("adn_nchw_slice_to_nhwc", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((nchw_to_nhwc_kernel<T>), dim3(blocks_for(n)), dim3(256), 0, st, s0, adn_as<T>(dst), B, C, c_pad,
+                       (int64_t)H * W, (int64_t)C_total);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int adn_nchw_to_nhwc(const float* src, void* dst, int32_t B, int32_t C, int32_t c_pad, int32_t H,
@@ -612,17 +616,16 @@ extern "C" int adn_nchw_to_nhwc(const float* src, void* dst, int32_t B, int32_t 
 extern "C" int adn_nhwc_to_nchw(const void* src, float* dst, int32_t B, int32_t C, int32_t H, int32_t W,
                                 int32_t dtype, void* stream) {
   ADN_CHECK_ARG(src && dst && B > 0 && C > 0 && H > 0 && W > 0, "adn_nhwc_to_nchw: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_nhwc_to_nchw: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_nhwc_to_nchw", dtype);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t n = (int64_t)B * C * H * W;
-  if (dtype == ADN_BF16)
-    hipLaunchKernelGGL((nhwc_to_nchw_kernel<uint16_t>), dim3(blocks_for(n)), dim3(256), 0, st,
-                       reinterpret_cast<const uint16_t*>(src), dst, B, C, (int64_t)H * W);
-  else
-    hipLaunchKernelGGL((nhwc_to_nchw_kernel<float>), dim3(blocks_for(n)), dim3(256), 0, st,
-                       reinterpret_cast<const float*>(src), dst, B, C, (int64_t)H * W);
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype("adn_nhwc_to_nchw", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((nhwc_to_nchw_kernel<T>), dim3(blocks_for(n)), dim3(256), 0, st, adn_as<T>(src), dst, B, C,
+                       (int64_t)H * W);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int adn_bn_fwd_finalize(const float* partials, int64_t P, int32_t C, int64_t count, const float* gamma,
@@ -655,35 +658,33 @@ extern "C" int adn_bn_eval_affine(const float* gamma, const float* beta, const f
   return ADN_OK;
 }
 
-extern "C" int adn_bn_act(const void* z, int64_t pixels, int32_t C, int32_t dtype, const float* scale,
-                          const float* shift, float slope, void* out_leaky, void* out_relu, void* stream) {
-  ADN_CHECK_ARG(z && pixels > 0 && C > 0 && scale && shift && (out_leaky || out_relu), "adn_bn_act: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_bn_act: bad dtype %d", dtype);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int64_t work = (C & 7) == 0 ? pixels * C / 8 : pixels * C;
-  if (dtype == ADN_BF16)
-    hipLaunchKernelGGL((bn_act_kernel<uint16_t>), dim3(bn_blocks_for(work)), dim3(256), 0, st,
-                       reinterpret_cast<const uint16_t*>(z), pixels, C, scale, shift, slope,
-                       reinterpret_cast<uint16_t*>(out_leaky), reinterpret_cast<uint16_t*>(out_relu));
-  else
-    hipLaunchKernelGGL((bn_act_kernel<float>), dim3(bn_blocks_for(work)), dim3(256), 0, st,
-                       reinterpret_cast<const float*>(z), pixels, C, scale, shift, slope,
-                       reinterpret_cast<float*>(out_leaky), reinterpret_cast<float*>(out_relu));
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
-}
-
 // BN apply + ReLU with an additional MX-fp8 copy (e4m3 + E8M0 per 32 channels) of the bf16 output, for the fp8 conv path.
+// (Ahead of adn_bn_act on purpose: kernels are emitted in the order in which they are first named, and this keeps
+// bn_act_kernel<bf16> in front of <f32> in the code object, where it was before the dispatcher.)
 extern "C" int adn_bn_act_mx8(const void* z, int64_t pixels, int32_t C, const float* scale, const float* shift,
                               void* out_relu, void* out8, void* out_scales, void* stream) {
   ADN_CHECK_ARG(z && pixels > 0 && C > 0 && C % 32 == 0 && scale && shift && out_relu && out8 && out_scales,
                 "adn_bn_act_mx8: bad arguments (C=%d must be a multiple of 32)", C);
   hipLaunchKernelGGL((bn_act_kernel<uint16_t>), dim3(bn_blocks_for(pixels * C / 8)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const uint16_t*>(z), pixels, C, scale, shift, 0.f,
-                     (uint16_t*)nullptr, reinterpret_cast<uint16_t*>(out_relu), reinterpret_cast<uint2*>(out8),
-                     reinterpret_cast<uint8_t*>(out_scales));
+                     reinterpret_cast<hipStream_t>(stream), adn_as<uint16_t>(z), pixels, C, scale, shift, 0.f,
+                     (uint16_t*)nullptr, adn_as<uint16_t>(out_relu), adn_as<uint2>(out8), adn_as<uint8_t>(out_scales));
   ADN_CHECK_LAUNCH();
   return ADN_OK;
+}
+
+extern "C" int adn_bn_act(const void* z, int64_t pixels, int32_t C, int32_t dtype, const float* scale,
+                          const float* shift, float slope, void* out_leaky, void* out_relu, void* stream) {
+  ADN_CHECK_ARG(z && pixels > 0 && C > 0 && scale && shift && (out_leaky || out_relu), "adn_bn_act: bad arguments");
+  ADN_CHECK_DTYPE("adn_bn_act", dtype);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t work = (C & 7) == 0 ? pixels * C / 8 : pixels * C;
+  return adn_by_dtype("adn_bn_act", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((bn_act_kernel<T>), dim3(bn_blocks_for(work)), dim3(256), 0, st, adn_as<T>(z), pixels, C, scale,
+                       shift, slope, adn_as<T>(out_leaky), adn_as<T>(out_relu));
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int adn_bn_bwd_apply_mx8(void* g, const void* z, int64_t pixels, int32_t C, const float* scale, const float* mean,
@@ -691,9 +692,8 @@ extern "C" int adn_bn_bwd_apply_mx8(void* g, const void* z, int64_t pixels, int3
   ADN_CHECK_ARG(g && z && pixels > 0 && C > 0 && C % 32 == 0 && scale && mean && istd && coef && out8 && out_scales,
                 "adn_bn_bwd_apply_mx8: bad arguments (C=%d must be a multiple of 32)", C);
   hipLaunchKernelGGL((bn_bwd_apply_kernel<uint16_t>), dim3(bn_blocks_for(pixels * C / 8)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), reinterpret_cast<uint16_t*>(g),
-                     reinterpret_cast<const uint16_t*>(z), pixels, C, scale, mean, istd, coef,
-                     reinterpret_cast<uint2*>(out8), reinterpret_cast<uint8_t*>(out_scales));
+                     reinterpret_cast<hipStream_t>(stream), adn_as<uint16_t>(g), adn_as<uint16_t>(z), pixels, C, scale,
+                     mean, istd, coef, adn_as<uint2>(out8), adn_as<uint8_t>(out_scales));
   ADN_CHECK_LAUNCH();
   return ADN_OK;
 }
@@ -758,19 +758,16 @@ extern "C" int adn_bn_bwd_finalize(const float* partials, int64_t P, int32_t C, 
 extern "C" int adn_bn_bwd_apply(void* g, const void* z, int64_t pixels, int32_t C, int32_t dtype, const float* scale,
                                 const float* mean, const float* istd, const float* coef, void* stream) {
   ADN_CHECK_ARG(g && z && pixels > 0 && C > 0 && scale && mean && istd && coef, "adn_bn_bwd_apply: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_bn_bwd_apply: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_bn_bwd_apply", dtype);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t work = (C & 7) == 0 ? pixels * C / 8 : pixels * C;
-  if (dtype == ADN_BF16)
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<uint16_t>), dim3(bn_blocks_for(work)), dim3(256), 0, st,
-                       reinterpret_cast<uint16_t*>(g), reinterpret_cast<const uint16_t*>(z), pixels, C, scale, mean,
-                       istd, coef);
-  else
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<float>), dim3(bn_blocks_for(work)), dim3(256), 0, st,
-                       reinterpret_cast<float*>(g), reinterpret_cast<const float*>(z), pixels, C, scale, mean, istd,
-                       coef);
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype("adn_bn_bwd_apply", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), dim3(bn_blocks_for(work)), dim3(256), 0, st, adn_as<T>(g), adn_as<T>(z),
+                       pixels, C, scale, mean, istd, coef);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 
@@ -793,21 +790,17 @@ extern "C" int adn_bn_fwd_fused(const float* partials, int64_t P, int32_t C, int
                 "adn_bn_fwd_fused: bad arguments");
   ADN_CHECK_ARG(C % 32 == 0, "adn_bn_fwd_fused: C must be a multiple of 32 (got %d)", C);
   ADN_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "adn_bn_fwd_fused: running stats mismatch");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_bn_fwd_fused: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_bn_fwd_fused", dtype);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)(C / 32), bn_fused_slices(pixels, C));
-  if (dtype == ADN_BF16)
-    hipLaunchKernelGGL((bn_fwd_fused_kernel<uint16_t>), grid, dim3(256), 0, st, partials, P, C, (double)count, gamma, beta,
-                       eps, momentum, running_mean, running_var, num_batches_tracked, mean, istd, scale, shift,
-                       reinterpret_cast<const uint16_t*>(z), pixels, slope, reinterpret_cast<uint16_t*>(out_leaky),
-                       reinterpret_cast<uint16_t*>(out_relu));
-  else
-    hipLaunchKernelGGL((bn_fwd_fused_kernel<float>), grid, dim3(256), 0, st, partials, P, C, (double)count, gamma, beta,
-                       eps, momentum, running_mean, running_var, num_batches_tracked, mean, istd, scale, shift,
-                       reinterpret_cast<const float*>(z), pixels, slope, reinterpret_cast<float*>(out_leaky),
-                       reinterpret_cast<float*>(out_relu));
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype("adn_bn_fwd_fused", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((bn_fwd_fused_kernel<T>), grid, dim3(256), 0, st, partials, P, C, (double)count, gamma, beta, eps,
+                       momentum, running_mean, running_var, num_batches_tracked, mean, istd, scale, shift, adn_as<T>(z),
+                       pixels, slope, adn_as<T>(out_leaky), adn_as<T>(out_relu));
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int adn_bn_bwd_fused(const float* partials, int64_t P, int32_t C, int64_t count, float* dgamma, float* dbeta,
@@ -816,38 +809,36 @@ extern "C" int adn_bn_bwd_fused(const float* partials, int64_t P, int32_t C, int
   ADN_CHECK_ARG(partials && P > 0 && C > 0 && count > 0 && g && z && pixels > 0 && scale && mean && istd,
                 "adn_bn_bwd_fused: bad arguments");
   ADN_CHECK_ARG(C % 32 == 0, "adn_bn_bwd_fused: C must be a multiple of 32 (got %d)", C);
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_bn_bwd_fused: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_bn_bwd_fused", dtype);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)(C / 32), bn_fused_slices(pixels, C));
-  if (dtype == ADN_BF16)
-    hipLaunchKernelGGL((bn_bwd_fused_kernel<uint16_t>), grid, dim3(256), 0, st, partials, P, C, (double)count, dgamma,
-                       dbeta, reinterpret_cast<uint16_t*>(g), reinterpret_cast<const uint16_t*>(z), pixels, scale, mean,
-                       istd);
-  else
-    hipLaunchKernelGGL((bn_bwd_fused_kernel<float>), grid, dim3(256), 0, st, partials, P, C, (double)count, dgamma, dbeta,
-                       reinterpret_cast<float*>(g), reinterpret_cast<const float*>(z), pixels, scale, mean, istd);
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype("adn_bn_bwd_fused", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((bn_bwd_fused_kernel<T>), grid, dim3(256), 0, st, partials, P, C, (double)count, dgamma, dbeta,
+                       adn_as<T>(g), adn_as<T>(z), pixels, scale, mean, istd);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int adn_pack_t2_multi(const void* flat_master, int32_t master_dtype, const int64_t* table, int32_t layers,
                                  int64_t total_blocks, int32_t dtype, void* t2_base, void* stream) {
   ADN_CHECK_ARG(flat_master && table && layers > 0 && total_blocks > 0 && t2_base, "adn_pack_t2_multi: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_pack_t2_multi: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_pack_t2_multi", dtype);
   ADN_CHECK_ARG(master_dtype == ADN_F32 || (master_dtype == ADN_BF16 && dtype == ADN_BF16),
                 "adn_pack_t2_multi: master dtype %d cannot feed a dtype-%d pack", master_dtype, dtype);
   ADN_CHECK_ARG(total_blocks < (1ll << 31), "adn_pack_t2_multi: too many blocks");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (master_dtype == ADN_BF16)
-    hipLaunchKernelGGL((pack_t2_multi_kernel<uint16_t, uint16_t>), dim3((unsigned)total_blocks), dim3(256), 0, st,
-                       reinterpret_cast<const uint16_t*>(flat_master), table, layers,
-                       reinterpret_cast<uint16_t*>(t2_base));
-  else if (dtype == ADN_BF16)
-    hipLaunchKernelGGL((pack_t2_multi_kernel<float, uint16_t>), dim3((unsigned)total_blocks), dim3(256), 0, st,
-                       reinterpret_cast<const float*>(flat_master), table, layers, reinterpret_cast<uint16_t*>(t2_base));
-  else
-    hipLaunchKernelGGL((pack_t2_multi_kernel<float, float>), dim3((unsigned)total_blocks), dim3(256), 0, st,
-                       reinterpret_cast<const float*>(flat_master), table, layers, reinterpret_cast<float*>(t2_base));
+  // master x pack is a three-way choice (a bf16 master never feeds an f32 pack: checked above), so no adn_by_dtype here
+  auto launch = [&](auto s, auto t) {
+    using S = decltype(s);
+    using T = decltype(t);
+    hipLaunchKernelGGL((pack_t2_multi_kernel<S, T>), dim3((unsigned)total_blocks), dim3(256), 0, st,
+                       adn_as<S>(flat_master), table, layers, adn_as<T>(t2_base));
+  };
+  if (master_dtype == ADN_BF16) launch(uint16_t{}, uint16_t{});
+  else if (dtype == ADN_BF16) launch(float{}, uint16_t{});
+  else launch(float{}, float{});
   ADN_CHECK_LAUNCH();
   return ADN_OK;
 }
@@ -856,32 +847,30 @@ extern "C" int adn_pack_rows(const float* master, int32_t X, int32_t taps, int32
                              int32_t dtype, void* out, void* stream) {
   ADN_CHECK_ARG(master && out && X > 0 && taps > 0 && Y > 0 && y_pad >= Y && row_stride >= taps * y_pad,
                 "adn_pack_rows: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_pack_rows: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_pack_rows", dtype);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t n = (int64_t)X * row_stride;
-  if (dtype == ADN_BF16)
-    hipLaunchKernelGGL((pack_rows_kernel<uint16_t>), dim3(blocks_for(n)), dim3(256), 0, st, master, X, taps, Y, y_pad,
-                       row_stride, reinterpret_cast<uint16_t*>(out));
-  else
-    hipLaunchKernelGGL((pack_rows_kernel<float>), dim3(blocks_for(n)), dim3(256), 0, st, master, X, taps, Y, y_pad,
-                       row_stride, reinterpret_cast<float*>(out));
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype("adn_pack_rows", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((pack_rows_kernel<T>), dim3(blocks_for(n)), dim3(256), 0, st, master, X, taps, Y, y_pad, row_stride,
+                       adn_as<T>(out));
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int adn_pack_transpose_taps(const float* master, int32_t X, int32_t taps, int32_t Y, int32_t flip,
                                        int32_t row_stride, int32_t dtype, void* out, void* stream) {
   ADN_CHECK_ARG(master && out && X > 0 && taps > 0 && Y > 0 && row_stride >= taps * X,
                 "adn_pack_transpose_taps: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_pack_transpose_taps: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_pack_transpose_taps", dtype);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)(adn_cdiv(X, 32) * adn_cdiv(Y, 32)), taps);
-  if (dtype == ADN_BF16)
-    hipLaunchKernelGGL((pack_transpose_taps_kernel<uint16_t>), grid, dim3(256), 0, st, master, X, taps, Y, flip,
-                       row_stride, reinterpret_cast<uint16_t*>(out));
-  else
-    hipLaunchKernelGGL((pack_transpose_taps_kernel<float>), grid, dim3(256), 0, st, master, X, taps, Y, flip,
-                       row_stride, reinterpret_cast<float*>(out));
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype("adn_pack_transpose_taps", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((pack_transpose_taps_kernel<T>), grid, dim3(256), 0, st, master, X, taps, Y, flip, row_stride,
+                       adn_as<T>(out));
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }

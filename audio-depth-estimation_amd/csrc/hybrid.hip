@@ -135,7 +135,7 @@ extern "C" int adn_hybrid_loss(const AdnHybridLoss* d, void* stream) {
   ADN_CHECK_ARG(d && d->logits && d->centers && d->coarse && d->offset && d->bins && d->gt && d->final_depth && d->dlogits &&
                     d->doffset && d->workspace && d->pixels > 0,
                 "adn_hybrid_loss: null operand or no pixels");
-  ADN_CHECK_ARG(d->dtype == ADN_F32 || d->dtype == ADN_BF16, "adn_hybrid_loss: bad dtype %d", d->dtype);
+  ADN_CHECK_DTYPE("adn_hybrid_loss", d->dtype);
   ADN_CHECK_ARG(d->nb >= 2 && d->nb <= kMaxNb, "adn_hybrid_loss: n_bins %d outside the supported range [2, %d]", d->nb, kMaxNb);
   ADN_CHECK_ARG(d->ld >= d->nb, "adn_hybrid_loss: row stride %d < n_bins %d", d->ld, d->nb);
   ADN_CHECK_ARG(d->workspace_bytes >= adn_hybrid_loss_workspace_bytes(d->pixels),
@@ -160,9 +160,10 @@ extern "C" int adn_hybrid_loss(const AdnHybridLoss* d, void* stream) {
   p.inv_nb = 1.f / (float)d->nb;
   p.smooth = d->label_smoothing / (float)d->nb;
   const dim3 grid(loss_blocks(d->pixels));
-  launch_bin_rows(d->dtype, d->nb, d->ld, d->logits, d->dlogits, [&](auto row) {
+  const int rc = launch_bin_rows("adn_hybrid_loss", d->dtype, d->nb, d->ld, d->logits, d->dlogits, [&](auto row) {
     hipLaunchKernelGGL((hybrid_loss_kernel<typename decltype(row)::type>), grid, dim3(256), 0, st, p);
   });
+  if (rc != ADN_OK) return rc;
   ADN_CHECK_LAUNCH();
   return ADN_OK;
 }

@@ -1393,7 +1393,7 @@ int run(const AdnIgemmDesc* d, const Plan& pl, hipStream_t st) {
 
 int validate(const AdnIgemmDesc* d) {
   ADN_CHECK_ARG(d != nullptr, "adn_igemm: null descriptor");
-  ADN_CHECK_ARG(d->dtype == ADN_F32 || d->dtype == ADN_BF16, "adn_igemm: bad dtype %d", d->dtype);
+  ADN_CHECK_DTYPE("adn_igemm", d->dtype);
   ADN_CHECK_ARG(d->geom == ADN_GEMM_S2 || d->geom == ADN_GEMM_T2 || d->geom == ADN_GEMM_S1, "adn_igemm: bad geom %d",
                 d->geom);
   ADN_CHECK_ARG(d->geom != ADN_GEMM_S1 || d->ks == 1 || d->ks == 3, "adn_igemm: S1 kernel side must be 1 or 3 (got %d)",
@@ -1462,6 +1462,5 @@ extern "C" int adn_igemm(const AdnIgemmDesc* d, void* stream) {
                 "adn_igemm: workspace too small (%lld < %lld)", (long long)d->workspace_bytes,
                 (long long)pl.slab_bytes);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d->dtype == ADN_BF16) return run<uint16_t>(d, pl, st);
-  return run<float>(d, pl, st);
+  return adn_by_dtype("adn_igemm", d->dtype, [&](auto t) { return run<decltype(t)>(d, pl, st); });
 }

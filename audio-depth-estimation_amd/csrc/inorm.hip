@@ -349,7 +349,7 @@ int pow2_ceil(int v) {
 
 // tensors: slices a workgroup keeps in LDS (forward 1, resident backward 2, streaming backward 0)
 bool make_plan(int HW, int C, int dtype, bool bwd, Plan* p) {
-  const int esz = dtype == ADN_BF16 ? 2 : 4;
+  const int esz = adn_dtype_bytes(dtype);
   p->vec = (C % 8 == 0) ? 8 : 1;
   p->resident = HW <= kSlabRows;
   p->S = (int)adn_cdiv(HW, kSlabRows);
@@ -373,7 +373,7 @@ bool aligned(const void* ptr, int bytes) { return (reinterpret_cast<uintptr_t>(p
 
 int check_common(const char* who, int32_t B, int32_t HW, int32_t C, int32_t dtype, const void* workspace,
                  int64_t workspace_bytes, Plan* p, bool bwd) {
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "%s: bad dtype %d", who, dtype);
+  ADN_CHECK_DTYPE(who, dtype);
   ADN_CHECK_ARG(B > 0 && B <= 65535 && C > 0 && (int64_t)B * C < (1ll << 31), "%s: bad shape B=%d C=%d", who, B, C);
   ADN_CHECK_ARG(HW >= 2, "%s: HW=%d: instance statistics need more than 1 spatial element", who, HW);
   ADN_CHECK_ARG(HW <= 65535 * kSlabRows, "%s: HW=%d too large", who, HW);
@@ -440,28 +440,23 @@ extern "C" int64_t adn_inorm_workspace_bytes(int32_t B, int32_t HW, int32_t C) {
 
 extern "C" int adn_dropout_apply(void* x, const uint8_t* keep, int64_t n, int32_t dtype, float scale, void* stream) {
   ADN_CHECK_ARG(x && n > 0, "adn_dropout_apply: null tensor or n=%lld", (long long)n);
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_dropout_apply: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_dropout_apply", dtype);
   const bool vec = n % 8 == 0 && aligned(x, 16) && aligned(keep, 8);
-  ADN_CHECK_ARG(aligned(x, dtype == ADN_BF16 ? 2 : 4), "adn_dropout_apply: misaligned tensor");
+  ADN_CHECK_ARG(aligned(x, adn_dtype_bytes(dtype)), "adn_dropout_apply: misaligned tensor");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)adn_grid_blocks(vec ? n / 8 : n, kThreads, 4096));
-#define ADN_DROP(T, VEC) \
-  hipLaunchKernelGGL((dropout_apply_kernel<T, VEC>), grid, dim3(kThreads), 0, st, reinterpret_cast<T*>(x), keep, n, scale)
-  if (dtype == ADN_BF16) {
-    if (vec) ADN_DROP(uint16_t, 8);
-    else ADN_DROP(uint16_t, 1);
-  } else {
-    if (vec) ADN_DROP(float, 8);
-    else ADN_DROP(float, 1);
-  }
-#undef ADN_DROP
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype_v("adn_dropout_apply", dtype, vec, [&](auto t, auto v) {
+    using T = decltype(t);
+    constexpr int VEC = decltype(v)::value;
+    hipLaunchKernelGGL((dropout_apply_kernel<T, VEC>), grid, dim3(kThreads), 0, st, adn_as<T>(x), keep, n, scale);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int adn_inorm_form(int32_t HW, int32_t C, int32_t dtype) {
   Plan p;
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_inorm_form: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_inorm_form", dtype);
   ADN_CHECK_ARG(HW >= 2 && C > 0, "adn_inorm_form: bad shape HW=%d C=%d", HW, C);
   ADN_CHECK_ARG(make_plan(HW, C, dtype, false, &p) && make_plan(HW, C, dtype, true, &p),
                 "adn_inorm_form: no plan for HW=%d C=%d", HW, C);
@@ -475,22 +470,17 @@ extern "C" int adn_inorm_fwd(const void* z, int32_t B, int32_t HW, int32_t C, in
   const int rc = check_common("adn_inorm_fwd", B, HW, C, dtype, workspace, workspace_bytes, &p, false);
   if (rc != ADN_OK) return rc;
   ADN_CHECK_ARG(z && mean && istd && (out_leaky || out_relu) && eps > 0.f, "adn_inorm_fwd: null argument or eps <= 0");
-  const int al = p.vec == 8 ? 16 : (dtype == ADN_BF16 ? 2 : 4);
+  const int al = p.vec == 8 ? 16 : adn_dtype_bytes(dtype);
   ADN_CHECK_ARG(aligned(z, al) && aligned(out_leaky, al) && aligned(out_relu, al) && aligned(mean, 4) &&
                     aligned(istd, 4) && aligned(keep, p.vec == 8 ? 8 : 1),
                 "adn_inorm_fwd: misaligned pointer (activations need %d bytes)", al);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   float* ws = reinterpret_cast<float*>(workspace);
-#define ADN_INORM_FWD(T, VEC)                                                                                      \
-  return launch_fwd<T, VEC>(p, reinterpret_cast<const T*>(z), B, HW, C, eps, slope, mean, istd,                    \
-                            reinterpret_cast<T*>(out_leaky), reinterpret_cast<T*>(out_relu), keep, keep_scale, ws, st)
-  if (dtype == ADN_BF16) {
-    if (p.vec == 8) ADN_INORM_FWD(uint16_t, 8);
-    ADN_INORM_FWD(uint16_t, 1);
-  }
-  if (p.vec == 8) ADN_INORM_FWD(float, 8);
-  ADN_INORM_FWD(float, 1);
-#undef ADN_INORM_FWD
+  return adn_by_dtype_v("adn_inorm_fwd", dtype, p.vec == 8, [&](auto t, auto v) {
+    using T = decltype(t);
+    return launch_fwd<T, decltype(v)::value>(p, adn_as<T>(z), B, HW, C, eps, slope, mean, istd, adn_as<T>(out_leaky),
+                                             adn_as<T>(out_relu), keep, keep_scale, ws, st);
+  });
 }
 
 extern "C" int adn_inorm_bwd(void* g, const void* z, const float* mean, const float* istd, int32_t B, int32_t HW,
@@ -500,18 +490,13 @@ extern "C" int adn_inorm_bwd(void* g, const void* z, const float* mean, const fl
   const int rc = check_common("adn_inorm_bwd", B, HW, C, dtype, workspace, workspace_bytes, &p, true);
   if (rc != ADN_OK) return rc;
   ADN_CHECK_ARG(g && z && mean && istd, "adn_inorm_bwd: null argument");
-  const int al = p.vec == 8 ? 16 : (dtype == ADN_BF16 ? 2 : 4);
+  const int al = p.vec == 8 ? 16 : adn_dtype_bytes(dtype);
   ADN_CHECK_ARG(aligned(g, al) && aligned(z, al) && aligned(mean, 4) && aligned(istd, 4),
                 "adn_inorm_bwd: misaligned pointer (activations need %d bytes)", al);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   float* ws = reinterpret_cast<float*>(workspace);
-#define ADN_INORM_BWD(T, VEC) \
-  return launch_bwd<T, VEC>(p, reinterpret_cast<T*>(g), reinterpret_cast<const T*>(z), B, HW, C, mean, istd, gscale, ws, st)
-  if (dtype == ADN_BF16) {
-    if (p.vec == 8) ADN_INORM_BWD(uint16_t, 8);
-    ADN_INORM_BWD(uint16_t, 1);
-  }
-  if (p.vec == 8) ADN_INORM_BWD(float, 8);
-  ADN_INORM_BWD(float, 1);
-#undef ADN_INORM_BWD
+  return adn_by_dtype_v("adn_inorm_bwd", dtype, p.vec == 8, [&](auto t, auto v) {
+    using T = decltype(t);
+    return launch_bwd<T, decltype(v)::value>(p, adn_as<T>(g), adn_as<T>(z), B, HW, C, mean, istd, gscale, ws, st);
+  });
 }

@@ -365,35 +365,34 @@ extern "C" int adn_loss_finish_dz(const float* pred, const float* gt, int64_t n,
 extern "C" int adn_final_act_bwd(const float* gout, const float* out, int64_t n, int32_t final_act, int32_t dtype,
                                  int32_t c_pad, void* dz, void* stream) {
   ADN_CHECK_ARG(gout && out && dz && n > 0 && c_pad >= 1, "adn_final_act_bwd: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_final_act_bwd: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_final_act_bwd", dtype);
   int64_t nb = adn_cdiv(n, 256);
   if (nb > 4096) nb = 4096;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == ADN_BF16)
-    hipLaunchKernelGGL((final_act_bwd_kernel<uint16_t>), dim3((unsigned)nb), dim3(256), 0, st, gout, out, n, final_act,
-                       c_pad, reinterpret_cast<uint16_t*>(dz));
-  else
-    hipLaunchKernelGGL((final_act_bwd_kernel<float>), dim3((unsigned)nb), dim3(256), 0, st, gout, out, n, final_act,
-                       c_pad, reinterpret_cast<float*>(dz));
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype("adn_final_act_bwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((final_act_bwd_kernel<T>), dim3((unsigned)nb), dim3(256), 0, st, gout, out, n, final_act, c_pad,
+                       adn_as<T>(dz));
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int adn_sum_to_scalar(const void* x, int64_t n, int32_t dtype, float* out, void* workspace,
                                  int64_t workspace_bytes, void* stream) {
   ADN_CHECK_ARG(x && out && n > 0 && workspace, "adn_sum_to_scalar: bad arguments");
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "adn_sum_to_scalar: bad dtype %d", dtype);
+  ADN_CHECK_DTYPE("adn_sum_to_scalar", dtype);
   const unsigned nb = red_blocks(n);
   ADN_CHECK_ARG(workspace_bytes >= (int64_t)nb * 8, "adn_sum_to_scalar: workspace too small");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   double* part = reinterpret_cast<double*>(workspace);
-  if (dtype == ADN_BF16)
-    hipLaunchKernelGGL((sum_partial_kernel<uint16_t>), dim3(nb), dim3(256), 0, st,
-                       reinterpret_cast<const uint16_t*>(x), n, part);
-  else
-    hipLaunchKernelGGL((sum_partial_kernel<float>), dim3(nb), dim3(256), 0, st, reinterpret_cast<const float*>(x), n,
-                       part);
-  ADN_CHECK_LAUNCH();
+  const int rc = adn_by_dtype("adn_sum_to_scalar", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((sum_partial_kernel<T>), dim3(nb), dim3(256), 0, st, adn_as<T>(x), n, part);
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
+  if (rc != ADN_OK) return rc;
   hipLaunchKernelGGL(sum_final_f32_kernel, dim3(1), dim3(256), 0, st, part, (int)nb, out);
   ADN_CHECK_LAUNCH();
   return ADN_OK;

@@ -171,10 +171,11 @@ struct WaveRow {
 };
 
 // Picks the layout of one launch and calls launch(RowTag<Row>()): the vector form needs bf16, unpadded rows of 8 LPP
-// bins, LPP a power of two, and 16-byte aligned logits and gradient (a NULL gradient counts as aligned).
+// bins, LPP a power of two, and 16-byte aligned logits and gradient (a NULL gradient counts as aligned).  Returns
+// ADN_OK, or ADN_ERR_ARG ("<who>: bad dtype <n>", nothing launched) for a dtype code it does not know.
 template <typename Row> struct RowTag { typedef Row type; };
 template <typename Launch>
-inline void launch_bin_rows(int dtype, int nb, int ld, const void* logits, const void* dlogits, Launch&& launch) {
+inline int launch_bin_rows(const char* who, int dtype, int nb, int ld, const void* logits, const void* dlogits, Launch&& launch) {
   const int lpp = nb / 8;
   const bool vec = dtype == ADN_BF16 && ld == nb && nb % 8 == 0 && (lpp & (lpp - 1)) == 0 &&
                    (reinterpret_cast<uintptr_t>(logits) & 15) == 0 && (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0;
@@ -184,9 +185,10 @@ inline void launch_bin_rows(int dtype, int nb, int ld, const void* logits, const
       ADN_VEC_ROW(1) ADN_VEC_ROW(2) ADN_VEC_ROW(4) ADN_VEC_ROW(8) ADN_VEC_ROW(16) ADN_VEC_ROW(32) ADN_VEC_ROW(64)
 #undef ADN_VEC_ROW
     }
-  } else if (dtype == ADN_BF16) {
-    launch(RowTag<WaveRow<uint16_t>>());
-  } else {
-    launch(RowTag<WaveRow<float>>());
+    return ADN_OK;
   }
+  return adn_by_dtype(who, dtype, [&](auto t) {
+    launch(RowTag<WaveRow<decltype(t)>>());
+    return ADN_OK;
+  });
 }

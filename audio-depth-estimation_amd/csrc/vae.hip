@@ -264,7 +264,7 @@ __global__ __launch_bounds__(256) void vae_bwd_enc_kernel(const float* __restric
 int vae_check(int32_t B, int32_t C, int32_t L, int32_t dtype, const char* who) {
   ADN_CHECK_ARG(B >= 1 && C >= 8 && C % 8 == 0 && L >= 1 && L <= 1024,
                 "%s: B %d, C %d, L %d (need B >= 1, C %% 8 == 0, 1 <= L <= 1024)", who, B, C, L);
-  ADN_CHECK_ARG(dtype == ADN_F32 || dtype == ADN_BF16, "%s: bad dtype %d", who, dtype);
+  ADN_CHECK_DTYPE(who, dtype);
   return ADN_OK;
 }
 
@@ -283,14 +283,13 @@ extern "C" int adn_vae_fwd(const float* h, int32_t B, int32_t C, int32_t L, cons
                      w_mu, b_mu, w_lv, b_lv, seed, counter, eps_in, mu, logvar, eps, z);
   ADN_CHECK_LAUNCH();
   const unsigned nb = (unsigned)adn_cdiv((int64_t)C * nbg, 4) + 1;
-  if (dtype == ADN_BF16)
-    hipLaunchKernelGGL((vae_decode_kernel<uint16_t>), dim3(nb), dim3(256), 0, st, z, B, B, C, L, w_dec, b_dec, mu, logvar,
-                       kl_img, kl, reinterpret_cast<uint16_t*>(out_relu));
-  else
-    hipLaunchKernelGGL((vae_decode_kernel<float>), dim3(nb), dim3(256), 0, st, z, B, B, C, L, w_dec, b_dec, mu, logvar,
-                       kl_img, kl, reinterpret_cast<float*>(out_relu));
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype("adn_vae_fwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((vae_decode_kernel<T>), dim3(nb), dim3(256), 0, st, z, B, B, C, L, w_dec, b_dec, mu, logvar, kl_img,
+                       kl, adn_as<T>(out_relu));
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int adn_vae_sample(const float* h, int32_t B, int32_t C, int32_t L, int32_t K, int32_t mode,
@@ -313,14 +312,13 @@ extern "C" int adn_vae_sample(const float* h, int32_t B, int32_t C, int32_t L, i
                      h, B, C, L, K, mode == ADN_VAE_DRAW ? 1 : 0, w_mu, b_mu, w_lv, b_lv, seed, eps_in, mu, logvar, eps, z);
   ADN_CHECK_LAUNCH();
   const unsigned nb = (unsigned)adn_cdiv((int64_t)C * nbg, 4) + 1;
-  if (dtype == ADN_BF16)
-    hipLaunchKernelGGL((vae_decode_kernel<uint16_t>), dim3(nb), dim3(256), 0, st, z, (int)rows, B, C, L, w_dec, b_dec, mu,
-                       logvar, kl_img, kl, reinterpret_cast<uint16_t*>(out_relu));
-  else
-    hipLaunchKernelGGL((vae_decode_kernel<float>), dim3(nb), dim3(256), 0, st, z, (int)rows, B, C, L, w_dec, b_dec, mu,
-                       logvar, kl_img, kl, reinterpret_cast<float*>(out_relu));
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+  return adn_by_dtype("adn_vae_sample", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((vae_decode_kernel<T>), dim3(nb), dim3(256), 0, st, z, (int)rows, B, C, L, w_dec, b_dec, mu, logvar,
+                       kl_img, kl, adn_as<T>(out_relu));
+    ADN_CHECK_LAUNCH();
+    return ADN_OK;
+  });
 }
 
 extern "C" int64_t adn_vae_bwd_workspace_bytes(int32_t B, int32_t L) {
@@ -343,20 +341,14 @@ extern "C" int adn_vae_bwd(const void* g_rec, int32_t dtype, int32_t B, int32_t 
   float* dmu_dlv = reinterpret_cast<float*>(workspace);
   const unsigned na = (unsigned)((int64_t)B * adn_cdiv(L, 64) + C);
   const unsigned nb = (unsigned)(2 * (int64_t)L + (int64_t)B * adn_cdiv(C, 64));
-  if (dtype == ADN_BF16) {
-    hipLaunchKernelGGL((vae_bwd_dec_kernel<uint16_t>), dim3(na), dim3(256), 0, st,
-                       reinterpret_cast<const uint16_t*>(g_rec), B, C, L, mu, logvar, eps, z, w_dec, g_kl, dw_dec, db_dec,
-                       dmu_dlv, kl, loss);
+  return adn_by_dtype("adn_vae_bwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((vae_bwd_dec_kernel<T>), dim3(na), dim3(256), 0, st, adn_as<T>(g_rec), B, C, L, mu, logvar, eps, z,
+                       w_dec, g_kl, dw_dec, db_dec, dmu_dlv, kl, loss);
     ADN_CHECK_LAUNCH();
-    hipLaunchKernelGGL((vae_bwd_enc_kernel<uint16_t>), dim3(nb), dim3(256), 0, st, h, B, C, L, w_mu, w_lv, dmu_dlv, dw_mu,
-                       db_mu, dw_lv, db_lv, reinterpret_cast<uint16_t*>(dh));
-  } else {
-    hipLaunchKernelGGL((vae_bwd_dec_kernel<float>), dim3(na), dim3(256), 0, st, reinterpret_cast<const float*>(g_rec), B,
-                       C, L, mu, logvar, eps, z, w_dec, g_kl, dw_dec, db_dec, dmu_dlv, kl, loss);
+    hipLaunchKernelGGL((vae_bwd_enc_kernel<T>), dim3(nb), dim3(256), 0, st, h, B, C, L, w_mu, w_lv, dmu_dlv, dw_mu, db_mu,
+                       dw_lv, db_lv, adn_as<T>(dh));
     ADN_CHECK_LAUNCH();
-    hipLaunchKernelGGL((vae_bwd_enc_kernel<float>), dim3(nb), dim3(256), 0, st, h, B, C, L, w_mu, w_lv, dmu_dlv, dw_mu,
-                       db_mu, dw_lv, db_lv, reinterpret_cast<float*>(dh));
-  }
-  ADN_CHECK_LAUNCH();
-  return ADN_OK;
+    return ADN_OK;
+  });
 }

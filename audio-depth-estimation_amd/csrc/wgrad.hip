@@ -604,7 +604,7 @@ void make_wplan(const AdnWgradDesc* d, WPlan* pl) {
 
 int wvalidate(const AdnWgradDesc* d) {
   ADN_CHECK_ARG(d != nullptr, "adn_wgrad: null descriptor");
-  ADN_CHECK_ARG(d->dtype == ADN_F32 || d->dtype == ADN_BF16, "adn_wgrad: bad dtype %d", d->dtype);
+  ADN_CHECK_DTYPE("adn_wgrad", d->dtype);
   ADN_CHECK_ARG(d->B > 0 && d->Hs > 0 && d->Ws > 0, "adn_wgrad: bad shape");
   ADN_CHECK_ARG(d->R0 > 0 && d->R1 >= 0 && d->C0 > 0 && d->C1 >= 0, "adn_wgrad: bad channels");
   ADN_CHECK_ARG(d->plain0 && d->gath0 && d->dw, "adn_wgrad: null operand");
@@ -745,8 +745,7 @@ extern "C" int adn_wgrad(const AdnWgradDesc* d, void* stream) {
     if (rc != ADN_OK) return rc;
     return slab_sum(reinterpret_cast<const float*>(d->workspace), d->dw, r.out_elems, r.nsplit, sq_of(d), st);
   }
-  if (d->dtype == ADN_BF16) return wrun<uint16_t>(d, r.pl, st);
-  return wrun<float>(d, r.pl, st);
+  return adn_by_dtype("adn_wgrad", d->dtype, [&](auto t) { return wrun<decltype(t)>(d, r.pl, st); });
 }
 
 // doubles adn_wgrad leaves in d->sq_partials: one per workgroup of the launch that writes the final dW (S1: none, see sq_of)
