@@ -262,6 +262,9 @@ _PROTOS = {
                                        c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
     'adn_convt_n1_forward_ex': (C.c_int, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32,
                                           c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
+    'adn_convt_n1_forward_bn': (C.c_int, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32,
+                                          c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
+                                          c_void_p, c_void_p]),
     'adn_l0_forward': (C.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p,
                                  c_void_p]),
     'adn_d0_dgrad_num_partials': (c_int64, [c_int32, c_int32, c_int32]),
@@ -275,6 +278,8 @@ _PROTOS = {
                                  c_void_p, c_int64, c_void_p]),
     'adn_thin_wgrad_ex': (C.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                     c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
+    'adn_thin_wgrad_bn': (C.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                    c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     'adn_sum_to_scalar': (C.c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
     'adn_grad_norm': (C.c_int, [c_void_p, c_int64, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
     'adn_grad_norm_workspace_bytes': (c_int64, [c_int64]),

@@ -46,19 +46,33 @@ __device__ __forceinline__ void load_tap_weights(const float* w, int nk, u32x4_t
   }
 }
 
+// BN1 (bf16): in1 holds the raw conv output z of a train-mode BatchNorm + ReLU layer; the kernel computes the activation
+// the materialised tensor would hold (bn_relu_chunk, epilogue.h) on every chunk after its load.  The scale / shift rows
+// [2][C1] sit in LDS behind the tap weights and are read per chunk (runtime channel index: not registers).
+__device__ __forceinline__ void load_bn_coef(const float* sc1, const float* sh1, int C1, float* cf) {
+  for (int e = threadIdx.x; e < C1; e += blockDim.x) {
+    cf[e] = sc1[e];
+    cf[C1 + e] = sh1[e];
+  }
+}
+
 // Two-launch form, first pass.  RELU0: in0 holds the values before the ReLU (see relu_chunk).
-template <typename T, bool RELU0>
+template <typename T, bool RELU0, bool BN1>
 __global__ __launch_bounds__(256) void convt_n1_partial_kernel(const T* in0, int C0, const T* in1, int C1,
-                                                               const float* w, int64_t M, float* P) {
+                                                               const float* w, int64_t M, float* P, const float* sc1,
+                                                               const float* sh1) {
+  static_assert(!BN1 || sizeof(T) == 2, "BN1 is a bf16 form");
   constexpr int EPC = 16 / (int)sizeof(T);
   constexpr int KS = 4 * EPC;                       // channels per MFMA step group (32 bf16 / 16 f32)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   u32x4_t* wl = reinterpret_cast<u32x4_t*>(smem);   // [nk][64 lanes]
   const int Cin = C0 + C1;
   const int nk = Cin / KS;
+  const float* cf = reinterpret_cast<const float*>(smem + nk * 1024);       // BN1: [2][C1]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fq = lane >> 4;
   load_tap_weights<T>(w, nk, wl);
+  if constexpr (BN1) load_bn_coef(sc1, sh1, C1, reinterpret_cast<float*>(smem + nk * 1024));
   __syncthreads();
   const int64_t groups = (M + 15) >> 4;
   const int nk0 = C0 / KS;
@@ -74,6 +88,7 @@ __global__ __launch_bounds__(256) void convt_n1_partial_kernel(const T* in0, int
           if constexpr (RELU0) a = relu_chunk<T>(a);
         } else {
           a = *reinterpret_cast<const u32x4_t*>(in1 + m * C1 + (s - nk0) * KS + fq * EPC);
+          if constexpr (BN1) a = bn_relu_chunk(a, cf + (s - nk0) * KS + fq * EPC, cf + C1 + (s - nk0) * KS + fq * EPC);
         }
       }
       const u32x4_t b = wl[s * 64 + lane];
@@ -120,20 +135,24 @@ constexpr int kFusedLds = 160 * 1024;               // LDS of a CU (gfx950); a t
 constexpr int kPStride = 17;                        // dwords per pixel in LDS: 16 taps + 1 (the gather walks every other
                                                     // pixel: 34-dword lane stride = 2-way bank conflicts, not 64-way)
 
-template <typename T, bool RELU0>
+template <typename T, bool RELU0, bool BN1>
 __global__ __launch_bounds__(kFusedThreads) void convt_n1_fused_kernel(const T* in0, int C0, const T* in1, int C1,
                                                                         const float* w, int Hs, int Ws, int TH,
-                                                                        const float* bias, int final_act, float* out) {
+                                                                        const float* bias, int final_act, float* out,
+                                                                        const float* sc1, const float* sh1) {
+  static_assert(!BN1 || sizeof(T) == 2, "BN1 is a bf16 form");
   constexpr int EPC = 16 / (int)sizeof(T);
   constexpr int KS = 4 * EPC;
   constexpr int NW = kFusedThreads / 64;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   u32x4_t* wl = reinterpret_cast<u32x4_t*>(smem);   // [nk][64 lanes]
   const int nk = (C0 + C1) / KS, nk0 = C0 / KS;
-  float* Pl = reinterpret_cast<float*>(smem + nk * 1024);       // [tile pixels][kPStride]
+  const float* cf = reinterpret_cast<const float*>(smem + nk * 1024);       // BN1: [2][C1] (see load_bn_coef)
+  float* Pl = reinterpret_cast<float*>(smem + nk * 1024 + (BN1 ? 2 * C1 * 4 : 0));       // [tile pixels][kPStride]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fq = lane >> 4;
   load_tap_weights<T>(w, nk, wl);
+  if constexpr (BN1) load_bn_coef(sc1, sh1, C1, reinterpret_cast<float*>(smem + nk * 1024));
   const int tpi = (Hs + TH - 1) / TH;               // tiles per image
   const int b = (int)blockIdx.x / tpi;
   const int r0 = ((int)blockIdx.x - b * tpi) * TH;
@@ -163,6 +182,8 @@ __global__ __launch_bounds__(kFusedThreads) void convt_n1_fused_kernel(const T* 
               if constexpr (RELU0) a[h][u] = relu_chunk<T>(a[h][u]);
             } else {
               a[h][u] = *reinterpret_cast<const u32x4_t*>(in1 + m * C1 + (s - nk0) * KS + fq * EPC);
+              if constexpr (BN1)
+                a[h][u] = bn_relu_chunk(a[h][u], cf + (s - nk0) * KS + fq * EPC, cf + C1 + (s - nk0) * KS + fq * EPC);
             }
           }
         }
@@ -232,28 +253,29 @@ inline int fused_tile_rows(int B, int Hs, int Ws, int wbytes) {
   return (int64_t)(th + 2) * Ws * kPStride * 4 + wbytes <= kFusedLds ? th : 0;
 }
 
-template <typename T, bool RELU0>
+template <typename T, bool RELU0, bool BN1>
 int launch_n1(int B, int Hs, int Ws, const void* in0, int C0, const void* in1, int C1, const float* w,
-              const float* bias, int final_act, float* out, float* P, bool two_launch, hipStream_t st) {
+              const float* bias, int final_act, float* out, float* P, bool two_launch, const float* sc1,
+              const float* sh1, hipStream_t st) {
   const int64_t M = (int64_t)B * Hs * Ws;
   const int nk = (C0 + C1) / (64 / (int)sizeof(T));
-  const int wbytes = nk * 64 * 16;
+  const int wbytes = nk * 64 * 16 + (BN1 ? 2 * C1 * 4 : 0);        // tap weights (+ the scale / shift rows of in1)
   const T* a0 = reinterpret_cast<const T*>(in0);
   const T* a1 = reinterpret_cast<const T*>(in1);
   const int th = two_launch ? 0 : fused_tile_rows(B, Hs, Ws, wbytes);
   if (th > 0) {
     const int rows = th < Hs ? th : Hs;
     const int lds = wbytes + (rows + 2) * Ws * kPStride * 4;
-    ADN_SET_LDS_ONCE(kFusedLds, &convt_n1_fused_kernel<T, RELU0>);
-    hipLaunchKernelGGL((convt_n1_fused_kernel<T, RELU0>), dim3((unsigned)(B * adn_cdiv(Hs, th))), dim3(kFusedThreads),
-                       lds, st, a0, C0, a1, C1, w, Hs, Ws, th, bias, final_act, out);
+    ADN_SET_LDS_ONCE(kFusedLds, &convt_n1_fused_kernel<T, RELU0, BN1>);
+    hipLaunchKernelGGL((convt_n1_fused_kernel<T, RELU0, BN1>), dim3((unsigned)(B * adn_cdiv(Hs, th))),
+                       dim3(kFusedThreads), lds, st, a0, C0, a1, C1, w, Hs, Ws, th, bias, final_act, out, sc1, sh1);
     ADN_CHECK_LAUNCH();
     return ADN_OK;
   }
   int64_t blocks = adn_cdiv(adn_cdiv(M, 16), 4);
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL((convt_n1_partial_kernel<T, RELU0>), dim3((unsigned)blocks), dim3(256), wbytes, st, a0, C0, a1, C1,
-                     w, M, P);
+  hipLaunchKernelGGL((convt_n1_partial_kernel<T, RELU0, BN1>), dim3((unsigned)blocks), dim3(256), wbytes, st, a0, C0, a1,
+                     C1, w, M, P, sc1, sh1);
   ADN_CHECK_LAUNCH();
   int64_t gb = adn_cdiv(M * 4, 256);
   if (gb > 4096) gb = 4096;
@@ -269,11 +291,14 @@ extern "C" int64_t adn_convt_n1_workspace_bytes(int32_t B, int32_t Hs, int32_t W
   return (int64_t)B * Hs * Ws * 16 * 4;
 }
 
-extern "C" int adn_convt_n1_forward_ex(int32_t dtype, int32_t B, int32_t Hs, int32_t Ws, const void* in0, int32_t C0,
+extern "C" int adn_convt_n1_forward_bn(int32_t dtype, int32_t B, int32_t Hs, int32_t Ws, const void* in0, int32_t C0,
                                        const void* in1, int32_t C1, const float* w, const float* bias,
                                        int32_t final_act, float* out, void* workspace, int64_t workspace_bytes,
-                                       int32_t flags, void* stream) {
+                                       int32_t flags, const float* scale1, const float* shift1, void* stream) {
   ADN_CHECK_DTYPE("adn_convt_n1_forward", dtype);
+  ADN_CHECK_ARG(!scale1 == !shift1, "adn_convt_n1_forward: scale1 and shift1 come together");
+  ADN_CHECK_ARG(!scale1 || (dtype == ADN_BF16 && C1 > 0 && in1),
+                "adn_convt_n1_forward: scale1 / shift1 need a bf16 in1 (the raw output of a BatchNorm + ReLU layer)");
   ADN_CHECK_ARG(B > 0 && Hs > 0 && Ws > 0 && C0 > 0 && C1 >= 0, "adn_convt_n1_forward: bad shape");
   ADN_CHECK_ARG(in0 && (C1 == 0 || in1) && w && out && workspace, "adn_convt_n1_forward: null operand");
   ADN_CHECK_ARG((flags & ~(ADN_N1_RELU_IN0 | ADN_N1_TWO_LAUNCH)) == 0, "adn_convt_n1_forward: bad flags %d", flags);
@@ -287,11 +312,26 @@ extern "C" int adn_convt_n1_forward_ex(int32_t dtype, int32_t B, int32_t Hs, int
   float* P = reinterpret_cast<float*>(workspace);
   const bool two = (flags & ADN_N1_TWO_LAUNCH) != 0;
   const bool relu0 = (flags & ADN_N1_RELU_IN0) != 0;
+  if (scale1)
+    return relu0 ? launch_n1<uint16_t, true, true>(B, Hs, Ws, in0, C0, in1, C1, w, bias, final_act, out, P, two, scale1,
+                                                   shift1, st)
+                 : launch_n1<uint16_t, false, true>(B, Hs, Ws, in0, C0, in1, C1, w, bias, final_act, out, P, two, scale1,
+                                                    shift1, st);
   return adn_by_dtype("adn_convt_n1_forward", dtype, [&](auto t) {
     using T = decltype(t);
-    return relu0 ? launch_n1<T, true>(B, Hs, Ws, in0, C0, in1, C1, w, bias, final_act, out, P, two, st)
-                 : launch_n1<T, false>(B, Hs, Ws, in0, C0, in1, C1, w, bias, final_act, out, P, two, st);
+    return relu0 ? launch_n1<T, true, false>(B, Hs, Ws, in0, C0, in1, C1, w, bias, final_act, out, P, two, nullptr,
+                                             nullptr, st)
+                 : launch_n1<T, false, false>(B, Hs, Ws, in0, C0, in1, C1, w, bias, final_act, out, P, two, nullptr,
+                                              nullptr, st);
   });
+}
+
+extern "C" int adn_convt_n1_forward_ex(int32_t dtype, int32_t B, int32_t Hs, int32_t Ws, const void* in0, int32_t C0,
+                                       const void* in1, int32_t C1, const float* w, const float* bias,
+                                       int32_t final_act, float* out, void* workspace, int64_t workspace_bytes,
+                                       int32_t flags, void* stream) {
+  return adn_convt_n1_forward_bn(dtype, B, Hs, Ws, in0, C0, in1, C1, w, bias, final_act, out, workspace,
+                                 workspace_bytes, flags, nullptr, nullptr, stream);
 }
 
 extern "C" int adn_convt_n1_forward(int32_t dtype, int32_t B, int32_t Hs, int32_t Ws, const void* in0, int32_t C0,

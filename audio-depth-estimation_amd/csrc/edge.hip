@@ -275,6 +275,11 @@ __global__ __launch_bounds__(256) void l0_fwd_stats_kernel(const float* __restri
 // ---------------------------------------------------------------------------------------------------------------------
 // Last transposed conv, input gradient.  dz [B][2Hs][2Ws] f32, w [128][16] f32 ([Cin][kh][kw][1]); segment 0 = skip
 // half, segment 1 = up half (ReLU mask by `ref`, optional BatchNorm-backward statistics of the segment).
+//
+// ZMASK: segment 1 has no materialised ReLU output to mask by (the BatchNorm + ReLU in front of it is applied by its
+// readers); the mask is (bn_relu_bf16_bits(z, scale, shift) > 0), the value the materialised tensor would hold, from
+// the z that the statistics load anyway: the ref read of the up half disappears.  The scale / shift rows sit in LDS:
+// 32 more loop-invariant registers are what an earlier mask-from-z form lost by.
 struct D0Params {
   const float* dz;
   const float* w;
@@ -282,8 +287,18 @@ struct D0Params {
   AdnEpiSeg seg[2];
 };
 
+template <bool ZMASK>
 __global__ __launch_bounds__(256) void d0_dgrad_kernel(D0Params p) {
+  enum { kScale, kShift };
+  __shared__ __attribute__((aligned(16))) float cf[ZMASK ? 2 : 1][64];
   __shared__ float red[4][2][64];
+  if constexpr (ZMASK) {
+    if (threadIdx.x < 64) {
+      cf[kScale][threadIdx.x] = p.seg[1].scale[threadIdx.x];
+      cf[kShift][threadIdx.x] = p.seg[1].shift[threadIdx.x];
+    }
+    __syncthreads();
+  }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = lane & 15, q = lane >> 4;
   const int Hs = p.Hs, Ws = p.Ws, Hl = 2 * Hs, Wl = 2 * Ws;
@@ -354,13 +369,15 @@ __global__ __launch_bounds__(256) void d0_dgrad_kernel(D0Params p) {
     // every epilogue operand of this pixel group is requested before the first use (6 x 16 bytes per lane in flight)
     u32x4_t rraw[2][2], zraw[2];
 #pragma unroll
-    for (int s = 0; s < 2; ++s)
+    for (int s = 0; s < 2; ++s) {
+      if (s == 1 && ZMASK) continue;
 #pragma unroll
       for (int h = 0; h < 2; ++h)
         rraw[s][h] = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const uint16_t*>(p.seg[s].ref) + pix * 64 + h * 32 +
                                                        q * 8);
+    }
     {
-      const uint16_t* zp = reinterpret_cast<const uint16_t*>(stats ? p.seg[1].z : p.seg[1].ref);
+      const uint16_t* zp = reinterpret_cast<const uint16_t*>(stats || ZMASK ? p.seg[1].z : p.seg[1].ref);
 #pragma unroll
       for (int h = 0; h < 2; ++h) zraw[h] = *reinterpret_cast<const u32x4_t*>(zp + pix * 64 + h * 32 + q * 8);
     }
@@ -374,8 +391,25 @@ __global__ __launch_bounds__(256) void d0_dgrad_kernel(D0Params p) {
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int64_t idx = pix * 64 + h * 32 + q * 8;
-        float r[8], gq[8];
-        Chunk<uint16_t>::unpack(rraw[s][h], r);
+        float r[8], gq[8], z[8];
+        if (s == 1) Chunk<uint16_t>::unpack(zraw[h], z);
+        if (s == 1 && ZMASK) {
+          float sc[8], sh[8];
+#pragma unroll
+          for (int v4 = 0; v4 < 2; ++v4) {
+            const f32x4_t a4 = *reinterpret_cast<const f32x4_t*>(&cf[kScale][h * 32 + q * 8 + v4 * 4]);
+            const f32x4_t b4 = *reinterpret_cast<const f32x4_t*>(&cf[kShift][h * 32 + q * 8 + v4 * 4]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              sc[v4 * 4 + e] = a4[e];
+              sh[v4 * 4 + e] = b4[e];
+            }
+          }
+#pragma unroll
+          for (int e = 0; e < 8; ++e) r[e] = bf16_bits_to_f32((uint16_t)bn_relu_bf16_bits(z[e], sc[e], sh[e]));
+        } else {
+          Chunk<uint16_t>::unpack(rraw[s][h], r);
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           gq[e] = acc[2 * h][e];
@@ -385,8 +419,6 @@ __global__ __launch_bounds__(256) void d0_dgrad_kernel(D0Params p) {
         for (int e = 0; e < 8; ++e) gq[e] *= (r[e] > 0.f ? 1.0f : sg.slope);
         store_bf16x8(reinterpret_cast<uint16_t*>(sg.out0) + idx, gq);
         if (s == 1) {
-          float z[8];
-          Chunk<uint16_t>::unpack(zraw[h], z);
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             s1[h * 8 + e] += gq[e];
@@ -435,11 +467,16 @@ struct TWParams {
   const uint16_t* plain1;
   int B, Hs, Ws;
   float* slab;       // [blocks][16*CT][C0+C1]
+  const float* sc1;  // BN1: scale / shift [C1] of the BatchNorm whose raw output plain1 is
+  const float* sh1;
 };
 
 // RELU0: plain0 holds the values before the ReLU; its fragments are clamped on their raw bits after the transposed
 // read (signed 16-bit max with 0: an element whose sign bit is set becomes +0, what fmaxf(v, 0.f) stores).
-template <int CT, int NT0, int NT1, bool RELU0>
+// BN1: plain1 holds the raw conv output z of a train-mode BatchNorm + ReLU layer; its fragments become the activation
+// the materialised tensor would hold (bn_relu_bf16_bits, epilogue.h) after the transposed read.  A lane's fragment of
+// tile t is 8 pixels of ONE channel (16 t + n), so it keeps one scale / shift pair per tile.
+template <int CT, int NT0, int NT1, bool RELU0, bool BN1 = false>
 __global__ __launch_bounds__(256) void thin_wgrad_kernel(TWParams p) {
   constexpr int NT = NT0 + NT1;
   constexpr int RB0 = NT0 * 32, RB1 = NT1 * 32;          // tile row bytes of the two plain sources
@@ -504,6 +541,14 @@ __global__ __launch_bounds__(256) void thin_wgrad_kernel(TWParams p) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[m][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
+  float sc1[NT1 > 0 ? NT1 : 1], sh1[NT1 > 0 ? NT1 : 1];
+  if constexpr (BN1) {
+#pragma unroll
+    for (int t = 0; t < NT1; ++t) {
+      sc1[t] = p.sc1[t * 16 + n];
+      sh1[t] = p.sh1[t * 16 + n];
+    }
+  }
   unsigned s = blockIdx.x * 4 + wave;
   float nxt[CT][8];
   if (s < steps) {
@@ -541,6 +586,13 @@ __global__ __launch_bounds__(256) void thin_wgrad_kernel(TWParams p) {
       s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
       if constexpr (RELU0) {
         if (t < NT0) v = __builtin_elementwise_max(v, s16x8_t{0, 0, 0, 0, 0, 0, 0, 0});
+      }
+      if constexpr (BN1) {
+        if (t >= NT0) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            v[e] = (short)bn_relu_bf16_bits(bf16_bits_to_f32((uint16_t)v[e]), sc1[tt], sh1[tt]);
+        }
       }
       const bf16x8_t bfr = *reinterpret_cast<bf16x8_t*>(&v);
 #pragma unroll
@@ -662,14 +714,18 @@ extern "C" int adn_d0_dgrad(const float* dz, const float* w, int32_t B, int32_t 
   p.seg[0] = *seg0;
   p.seg[1] = *seg1;
   for (int s = 0; s < 2; ++s) {
-    ADN_CHECK_ARG(p.seg[s].out0 && p.seg[s].ref, "adn_d0_dgrad: seg %d needs out0 and ref", s);
+    ADN_CHECK_ARG(p.seg[s].out0 && (p.seg[s].ref || (s == 1 && p.seg[s].z && p.seg[s].scale && p.seg[s].shift)),
+                  "adn_d0_dgrad: seg %d needs out0 and ref (seg 1: or z, scale and shift to mask by)", s);
     ADN_CHECK_ARG(!p.seg[s].partials || (p.seg[s].z && p.seg[s].mean && p.seg[s].istd),
                   "adn_d0_dgrad: seg %d statistics need z / mean / istd", s);
     ADN_CHECK_ARG(!p.seg[s].accumulate, "adn_d0_dgrad: accumulate is not supported");
   }
   ADN_CHECK_ARG(!p.seg[0].partials, "adn_d0_dgrad: statistics are produced for segment 1 only");
-  hipLaunchKernelGGL(d0_dgrad_kernel, dim3(edge_blocks((int64_t)B * Hs * (Ws / 16), kDgradBlocks)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), p);
+  const dim3 grid(edge_blocks((int64_t)B * Hs * (Ws / 16), kDgradBlocks));
+  if (p.seg[1].ref)
+    hipLaunchKernelGGL(d0_dgrad_kernel<false>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
+  else
+    hipLaunchKernelGGL(d0_dgrad_kernel<true>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
   ADN_CHECK_LAUNCH();
   return ADN_OK;
 }
@@ -679,11 +735,14 @@ extern "C" int64_t adn_thin_wgrad_workspace_bytes(int32_t B, int32_t Hs, int32_t
   return (int64_t)edge_blocks((int64_t)B * Hs * (Ws / 32), kWgradBlocks) * 16 * ct * (c0 + c1) * 4;
 }
 
-extern "C" int adn_thin_wgrad_ex(const float* thin, int32_t ct, const void* plain0, int32_t c0, const void* plain1,
+extern "C" int adn_thin_wgrad_bn(const float* thin, int32_t ct, const void* plain0, int32_t c0, const void* plain1,
                                  int32_t c1, int32_t B, int32_t Hs, int32_t Ws, float* dw, void* workspace,
-                                 int64_t workspace_bytes, int32_t relu_plain0, void* stream) {
+                                 int64_t workspace_bytes, int32_t relu_plain0, const float* scale1, const float* shift1,
+                                 void* stream) {
   ADN_CHECK_ARG(thin && plain0 && dw && workspace && (c1 == 0 || plain1), "adn_thin_wgrad: null operand");
   ADN_CHECK_ARG(!relu_plain0 || ct == 1, "adn_thin_wgrad: relu_plain0 is for the ct 1 form (plain0 = an activation)");
+  ADN_CHECK_ARG(!scale1 == !shift1 && (!scale1 || ct == 1),
+                "adn_thin_wgrad: scale1 and shift1 come together, for the ct 1 form (plain1 = a raw BatchNorm input)");
   ADN_CHECK_ARG(B > 0 && Hs > 0 && Ws > 0 && Ws % 32 == 0, "adn_thin_wgrad: bad shape B=%d Hs=%d Ws=%d (Ws %% 32)", B, Hs,
                 Ws);
   ADN_CHECK_ARG((ct == 1 && c0 == 64 && c1 == 64) || (ct == 2 && c0 == 64 && c1 == 0),
@@ -701,12 +760,20 @@ extern "C" int adn_thin_wgrad_ex(const float* thin, int32_t ct, const void* plai
   p.Hs = Hs;
   p.Ws = Ws;
   p.slab = reinterpret_cast<float*>(workspace);
+  p.sc1 = scale1;
+  p.sh1 = shift1;
   const int nblk = edge_blocks((int64_t)B * Hs * (Ws / 32), kWgradBlocks);
   const int rows = 16 * ct, ctot = c0 + c1;
   // LDS: 4 waves x 2 staging buffers x 32 pixels x (c0 + c1) bf16, reused as the [4][rows][ctot] f32 reduction tile
   const int stage = 4 * 2 * 32 * ctot * 2, redb = 4 * rows * ctot * 4;
   const int lds = stage > redb ? stage : redb;
-  if (ct == 1 && relu_plain0) {
+  if (scale1 && relu_plain0) {
+    ADN_SET_LDS_ONCE(lds, &thin_wgrad_kernel<1, 4, 4, true, true>);
+    hipLaunchKernelGGL((thin_wgrad_kernel<1, 4, 4, true, true>), dim3(nblk), dim3(256), lds, st, p);
+  } else if (scale1) {
+    ADN_SET_LDS_ONCE(lds, &thin_wgrad_kernel<1, 4, 4, false, true>);
+    hipLaunchKernelGGL((thin_wgrad_kernel<1, 4, 4, false, true>), dim3(nblk), dim3(256), lds, st, p);
+  } else if (ct == 1 && relu_plain0) {
     ADN_SET_LDS_ONCE(lds, &thin_wgrad_kernel<1, 4, 4, true>);
     hipLaunchKernelGGL((thin_wgrad_kernel<1, 4, 4, true>), dim3(nblk), dim3(256), lds, st, p);
   } else if (ct == 1) {
@@ -721,6 +788,13 @@ extern "C" int adn_thin_wgrad_ex(const float* thin, int32_t ct, const void* plai
                      rows, ctot, dw);
   ADN_CHECK_LAUNCH();
   return ADN_OK;
+}
+
+extern "C" int adn_thin_wgrad_ex(const float* thin, int32_t ct, const void* plain0, int32_t c0, const void* plain1,
+                                 int32_t c1, int32_t B, int32_t Hs, int32_t Ws, float* dw, void* workspace,
+                                 int64_t workspace_bytes, int32_t relu_plain0, void* stream) {
+  return adn_thin_wgrad_bn(thin, ct, plain0, c0, plain1, c1, B, Hs, Ws, dw, workspace, workspace_bytes, relu_plain0,
+                           nullptr, nullptr, stream);
 }
 
 extern "C" int adn_thin_wgrad(const float* thin, int32_t ct, const void* plain0, int32_t c0, const void* plain1,

@@ -303,9 +303,10 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const T* z, int64_t pixels,
       }
       float v[8], o[8];
       load8<T>(z, e, v);
-      // (forward apply: the same body stands in bn_fwd_fused_kernel -- change both.  A shared helper changed the kernel.)
+      // (forward apply: the same body stands in bn_fwd_fused_kernel -- change both.  bn_affine1, epilogue.h: scalars by
+      // value, shared with the kernels that apply this BatchNorm + ReLU on load instead of reading out_relu)
 #pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = v[k] * sc[k] + sh[k];
+      for (int k = 0; k < 8; ++k) v[k] = bn_affine1(v[k], sc[k], sh[k]);
       if (out_leaky) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) o[k] = v[k] > 0.f ? v[k] : v[k] * slope;

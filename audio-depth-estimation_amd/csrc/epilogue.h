@@ -76,6 +76,25 @@ __device__ __forceinline__ void store8(void* base, int64_t idx, const float* f) 
   }
 }
 
+// ---- BatchNorm apply, one element --------------------------------------------------------------------
+// Forward: the affine value bn_act_kernel activates, and the bf16 bits its ReLU copy holds for z.  The kernels that read
+// a BatchNorm + ReLU activation "virtually" (from z, scale and shift: convt_n1, thin_wgrad, d0_dgrad's mask) call the
+// same two functions, so the product and the sum are contracted the same way everywhere.
+__device__ __forceinline__ float bn_affine1(float z, float scale, float shift) { return z * scale + shift; }
+__device__ __forceinline__ uint32_t bn_relu_bf16_bits(float z, float scale, float shift) {
+  return f32_to_bf16_bits(fmaxf(bn_affine1(z, scale, shift), 0.f));
+}
+// bn_relu_bf16_bits over a 16-byte chunk of bf16 z (8 consecutive channels, coefficients sc[0..7] / sh[0..7])
+__device__ __forceinline__ u32x4_t bn_relu_chunk(const u32x4_t& zc, const float* sc, const float* sh) {
+  float z[8];
+  Chunk<uint16_t>::unpack(zc, z);
+  u32x4_t c;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    c[i] = bn_relu_bf16_bits(z[2 * i], sc[2 * i], sh[2 * i]) | (bn_relu_bf16_bits(z[2 * i + 1], sc[2 * i + 1], sh[2 * i + 1]) << 16);
+  return c;
+}
+
 // Per-thread constants of an 8-channel column group (hoisted out of the row loop).
 struct EpiCols {
   float a[8], b[8];  // ACT: scale, shift(+bias); BWD: mean, istd; FINAL: bias in b

@@ -179,7 +179,7 @@ class UNetEngine(FlatParamEngine):
                                f'actual input size')
 
     def _decide_edge_paths(self, Cin, W):
-        """How the two thin outermost layers run: cin_pad / cout_pad, n1_path, edge_path, skip0_leaky."""
+        """How the two thin outermost layers run: cin_pad / cout_pad, n1_path, edge_path, skip0_leaky, ru1_virtual_ok."""
         T, l0 = self.dtype, self.levels[0]
         epc = 8 if T == torch.bfloat16 else 4          # elements per 16-byte chunk
         # Edge layers: the first conv (Cin = 2) and the last transposed conv (Cout = 1) run on the MFMA
@@ -205,6 +205,16 @@ class UNetEngine(FlatParamEngine):
         # slope), so rd[0] is neither allocated nor written.  ADN_L0_TWO_COPIES=1 keeps the separate ReLU copy (A/B).
         self.skip0_leaky = (self.edge_path and self.n1_path and not self._no_skip(0)
                             and not os.environ.get('ADN_L0_TWO_COPIES'))
+        # Level 1's decoder output ru[1] = ReLU(BN(zu[1])) is the widest activation of the net and all of its readers are
+        # edge kernels that transform their operand in registers.  With a train-mode BatchNorm and no dropout behind D1 a
+        # training forward runs only bn_fwd_finalize for D1, and every reader (last transposed conv, its weight gradient,
+        # the mask of its input gradient) takes zu[1] with the BatchNorm's scale / shift and computes the value bn_act
+        # would have stored: ru[1] is neither written nor read (an eval forward still writes it).
+        # ADN_D1_MATERIALISED=1 keeps bn_act + the materialised ru[1] (A/B).
+        l1 = self.levels[1] if self.n > 1 else None
+        self.ru1_virtual_ok = bool(self.edge_path and not self._no_skip(0) and l1['bn_u'] is not None and not l1['in_u']
+                                   and not l1['drop'] and not os.environ.get('ADN_D1_MATERIALISED'))
+        self._ru1_virtual = False         # what the last D1 forward on this buffer set did (_up_conv); backward follows it
 
     def _build_sides(self, H, W):
         """The two Side records of every level: layer geometry, norm kind, weight-gradient problem."""
@@ -366,7 +376,17 @@ class UNetEngine(FlatParamEngine):
         L = self.levels
         if self._no_skip(i):
             return L[i + 1]['ru'], None
+        if i == 0 and self._ru1_virtual:                  # zu[1], to be read with _up_bn1(0)
+            return L[0]['skip'], L[1]['zu']
         return L[i]['skip'], (L[i + 1]['ru'] if i < self.n - 1 else None)
+
+    def _up_bn1(self, i):
+        """(scale, shift) when the second operand of _up_inputs(i) is the raw output of a BatchNorm + ReLU layer whose
+        readers apply both on load (level 0 after a training forward with ru1_virtual_ok), else None."""
+        if i == 0 and self._ru1_virtual:
+            u1 = self.levels[1]['u']
+            return u1.scale, u1.shift
+        return None
 
     def _skip_relu(self, i):
         """True when the first operand of _up_inputs(i) still needs its ReLU (the reader clamps it on load)."""
@@ -481,7 +501,7 @@ class UNetEngine(FlatParamEngine):
             K.igemm(T, GEMM_T2, B, s.hs, s.ws, in0, in1, s.t2, C, epi, [K.Seg(C, **seg)], ws)
         if i == 0 and self.n1_path:
             K.convt_n1_forward(T, B, s.hs, s.ws, in0, in1, self._flat_slice(self.flat_p, s.conv.weight), s.conv.bias,
-                               self.final_act, out, ws, relu_in0=self._skip_relu(i))
+                               self.final_act, out, ws, relu_in0=self._skip_relu(i), bn1=self._up_bn1(i))
         elif i == 0:
             gemm(EPI_FINAL, out0=out, bias=s.conv.bias, final_act=self.final_act)
         elif s.norm == 'instance':
@@ -491,11 +511,14 @@ class UNetEngine(FlatParamEngine):
             gemm(EPI_ACT, out1=ru)
         elif training:
             gemm(EPI_Z_STATS, out0=s.z, partials=s.part)
-            self._bn_forward(s, 0.0, None, ru)
+            virtual = i == 1 and self.ru1_virtual_ok      # the readers of ru[1] apply the BatchNorm + ReLU themselves
+            self._bn_forward(s, 0.0, None, ru, apply=not virtual)
         else:
             if affine:
                 self._eval_affine(s)
             gemm(EPI_ACT, out1=ru, scale=s.scale, shift=s.shift)
+        if i == 1:
+            self._ru1_virtual = bool(training) and s.norm == 'batch' and self.ru1_virtual_ok
         if keep is not None and s.norm != 'instance':     # (dropout levels are <= 8 x 8 images: an unfused pass over ru)
             K.dropout_apply(ru, keep, keep_scale)
 
@@ -506,15 +529,18 @@ class UNetEngine(FlatParamEngine):
     def _bn_one_launch(self, s):
         return self.B * s.px * s.C <= self.BN_FUSED_MAX and s.C % 32 == 0
 
-    def _bn_forward(self, s, slope, out_leaky, out_relu):
-        """Train-mode BatchNorm + activation of a side's raw conv output: statistics finalize (+ running stats), apply."""
+    def _bn_forward(self, s, slope, out_leaky, out_relu, apply=True):
+        """Train-mode BatchNorm + activation of a side's raw conv output: statistics finalize (+ running stats), apply.
+        ``apply=False``: the finalize alone (scale / shift for readers that apply them on load)."""
         bn, count = s.bn, self.B * s.px
         track = bn.track_running_stats and bn.running_mean is not None
         args = (s.part, s.P, s.C, count, bn.weight, bn.bias, BN_EPS,
                 BN_MOMENTUM if bn.momentum is None else bn.momentum,
                 bn.running_mean if track else None, bn.running_var if track else None,
                 bn.num_batches_tracked if track else None, s.mean, s.istd, s.scale, s.shift)
-        if self._bn_one_launch(s):
+        if not apply:
+            K.bn_fwd_finalize(*args)
+        elif self._bn_one_launch(s):
             K.bn_fwd_fused(*args, s.z, count, slope, out_leaky, out_relu)
         else:
             K.bn_fwd_finalize(*args)
@@ -566,7 +592,7 @@ class UNetEngine(FlatParamEngine):
             K.wgrad_multi(self.dtype, self.B, pend[MULTI])
             del pend[MULTI][:]
 
-    def _emit_wgrad(self, pend, s, plain0, plain1, gath, fused_norm, relu_plain0=False):
+    def _emit_wgrad(self, pend, s, plain0, plain1, gath, fused_norm, relu_plain0=False, bn1=None):
         """Weight gradient of side ``s`` by the route _prepare chose.  Nothing inside backward reads a dW and the operands
         stay untouched until the end of the pass, so the small-image problems are collected in ``pend[MULTI]`` (one
         adn_wgrad_multi launch per 8) and the members of a patch-staged group in ``pend[tag]`` until its trigger.  Under
@@ -578,7 +604,7 @@ class UNetEngine(FlatParamEngine):
         prob = (s.hs, s.ws, plain0, plain1, gath, None, dw, s.sq if fused_norm else None)
         ready = True
         if s.route == THIN:
-            K.thin_wgrad(gath, plain0, plain1, B, s.hs, s.ws, dw, ws, relu_plain0=relu_plain0)
+            K.thin_wgrad(gath, plain0, plain1, B, s.hs, s.ws, dw, ws, relu_plain0=relu_plain0, bn1=bn1)
         elif s.route == MULTI:
             if len(pend[MULTI]) == 8:
                 self._flush_wgrad(pend)
@@ -633,8 +659,9 @@ class UNetEngine(FlatParamEngine):
             segs = [] if self._no_skip(i) else [K.Seg(lv['cd_out'], out0=lv['Gd'], ref=lv['skip'], slope=0.0)]
             if i < n - 1:
                 nx = L[i + 1]
-                segs.append(self._grad_seg(nx['u'], nx['Gu'], nx['ru'], 0.0))
-            self._emit_wgrad(pend, s, in0, in1, dz, fused_norm, relu_plain0=self._skip_relu(i))
+                # (level 0 behind a forward that did not write ru[1]: no ref, d0_dgrad masks by z, scale and shift)
+                segs.append(self._grad_seg(nx['u'], nx['Gu'], None if i == 0 and self._ru1_virtual else nx['ru'], 0.0))
+            self._emit_wgrad(pend, s, in0, in1, dz, fused_norm, relu_plain0=self._skip_relu(i), bn1=self._up_bn1(i))
             if s.route == THIN:
                 K.d0_dgrad(dz, self._flat_slice(self.flat_p, s.conv.weight), B, s.hs, s.ws, segs[0], segs[1])
             else:

@@ -481,15 +481,25 @@ def convt_n1_workspace_bytes(B, Hs, Ws):
 N1_RELU_IN0, N1_TWO_LAUNCH = 1, 2          # adn.h: flags of adn_convt_n1_forward_ex
 
 
-def convt_n1_forward(dtype, B, Hs, Ws, in0, in1, w_master, bias, final_act, out, workspace, relu_in0=False):
+def convt_n1_forward(dtype, B, Hs, Ws, in0, in1, w_master, bias, final_act, out, workspace, relu_in0=False, bn1=None,
+                     two_launch=None):
     """Last transposed conv (Cout = 1).  ``relu_in0``: in0 holds the values before the ReLU (a LeakyReLU copy), the
-    kernel clamps it on load.  ADN_CONVT_N1_FUSED=0 takes the two-launch form (tap products through the workspace)."""
-    _dev(in0, in1, w_master, bias, out, workspace)
+    kernel clamps it on load.  ``bn1`` = (scale, shift): in1 holds the raw conv output of a train-mode BatchNorm + ReLU
+    layer, the kernel applies both on load (adn_convt_n1_forward_bn).  ADN_CONVT_N1_FUSED=0 (or ``two_launch``) takes the
+    two-launch form (tap products through the workspace)."""
+    sc1, sh1 = bn1 if bn1 is not None else (None, None)
+    _dev(in0, in1, w_master, bias, out, workspace, sc1, sh1)
     ev = _prof_begin()
-    flags = (N1_RELU_IN0 if relu_in0 else 0) | (N1_TWO_LAUNCH if os.environ.get('ADN_CONVT_N1_FUSED') == '0' else 0)
-    _lib.call('adn_convt_n1_forward_ex', dtype_code(dtype), B, Hs, Ws, ptr(in0), in0.shape[-1], ptr(in1),
-              in1.shape[-1] if in1 is not None else 0, ptr(w_master), ptr(bias), final_act, ptr(out), ptr(workspace),
-              workspace.numel() * workspace.element_size(), flags, _stream())
+    if two_launch is None:
+        two_launch = os.environ.get('ADN_CONVT_N1_FUSED') == '0'
+    flags = (N1_RELU_IN0 if relu_in0 else 0) | (N1_TWO_LAUNCH if two_launch else 0)
+    args = (dtype_code(dtype), B, Hs, Ws, ptr(in0), in0.shape[-1], ptr(in1), in1.shape[-1] if in1 is not None else 0,
+            ptr(w_master), ptr(bias), final_act, ptr(out), ptr(workspace), workspace.numel() * workspace.element_size(),
+            flags)
+    if bn1 is None:
+        _lib.call('adn_convt_n1_forward_ex', *args, _stream())
+    else:
+        _lib.call('adn_convt_n1_forward_bn', *args, ptr(sc1), ptr(sh1), _stream())
     if ev is not None:
         cin = in0.shape[-1] + (in1.shape[-1] if in1 is not None else 0)
         _prof_end(ev, 'convt_n1', 2.0 * B * Hs * Ws * 16 * cin)
@@ -524,7 +534,8 @@ def d0_dgrad_num_partials(B, Hs, Ws):
 
 
 def d0_dgrad(dz, w_master, B, Hs, Ws, seg0, seg1):
-    """Input gradient of the last transposed conv (128 -> 1): dz f32 [B,1,2Hs,2Ws], segments = skip / up half."""
+    """Input gradient of the last transposed conv (128 -> 1): dz f32 [B,1,2Hs,2Ws], segments = skip / up half.  seg1
+    without ``ref``: masked by the BatchNorm + ReLU of its z (scale, shift), the activation that was not materialised."""
     _dev(dz, w_master)
     s0, s1 = AdnEpiSeg(), AdnEpiSeg()
     seg0.fill(s0)
@@ -537,15 +548,22 @@ def thin_wgrad_workspace_bytes(B, Hs, Ws, ct, c0, c1):
     return _lib.load().adn_thin_wgrad_workspace_bytes(B, Hs, Ws, ct, c0, c1)
 
 
-def thin_wgrad(thin, plain0, plain1, B, Hs, Ws, dw, workspace, relu_plain0=False):
+def thin_wgrad(thin, plain0, plain1, B, Hs, Ws, dw, workspace, relu_plain0=False, bn1=None):
     """dw[c][tap*ct + t] = sum plain[.., c] * thin window; thin f32 [B,ct,2Hs,2Ws] planar, plain bf16 NHWC.
-    ``relu_plain0`` (ct = 1): plain0 holds the values before the ReLU, the kernel clamps it after the load."""
-    _dev(thin, plain0, plain1, dw, workspace)
+    ``relu_plain0`` (ct = 1): plain0 holds the values before the ReLU, the kernel clamps it after the load.
+    ``bn1`` = (scale, shift) (ct = 1): plain1 holds the raw conv output of a train-mode BatchNorm + ReLU layer, the kernel
+    applies both after the load (adn_thin_wgrad_bn)."""
+    sc1, sh1 = bn1 if bn1 is not None else (None, None)
+    _dev(thin, plain0, plain1, dw, workspace, sc1, sh1)
     ct = thin.shape[1]
     c0 = plain0.shape[-1]
     c1 = plain1.shape[-1] if plain1 is not None else 0
-    _lib.call('adn_thin_wgrad_ex', ptr(thin), ct, ptr(plain0), c0, ptr(plain1), c1, B, Hs, Ws, ptr(dw), ptr(workspace),
-              workspace.numel() * workspace.element_size(), 1 if relu_plain0 else 0, _stream())
+    args = (ptr(thin), ct, ptr(plain0), c0, ptr(plain1), c1, B, Hs, Ws, ptr(dw), ptr(workspace),
+            workspace.numel() * workspace.element_size(), 1 if relu_plain0 else 0)
+    if bn1 is None:
+        _lib.call('adn_thin_wgrad_ex', *args, _stream())
+    else:
+        _lib.call('adn_thin_wgrad_bn', *args, ptr(sc1), ptr(sh1), _stream())
     _lib.annotate(label='edge', flops=2.0 * B * Hs * Ws * (c0 + c1) * 16 * ct)
 
 

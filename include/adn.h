@@ -546,6 +546,14 @@ int adn_convt_n1_forward_ex(int32_t dtype, int32_t B, int32_t Hs, int32_t Ws, co
                             const void* in1, int32_t C1, const float* w, const float* bias,
                             int32_t final_act, float* out, void* workspace, int64_t workspace_bytes,
                             int32_t flags, void* stream);
+/* adn_convt_n1_forward_bn = _ex with in1 read "virtually": scale1 / shift1 (f32 [C1], both or neither; bf16 only) say
+ * that in1 holds the raw conv output z of a train-mode BatchNorm + ReLU layer, and the kernel computes on every 16-byte
+ * chunk after its load the value adn_bn_act's relu copy would hold, bf16(max(z * scale1 + shift1, 0)): the same bits as
+ * adn_bn_act into a buffer followed by _ex on that buffer, without the buffer.  NULL / NULL: exactly _ex. */
+int adn_convt_n1_forward_bn(int32_t dtype, int32_t B, int32_t Hs, int32_t Ws, const void* in0, int32_t C0,
+                            const void* in1, int32_t C1, const float* w, const float* bias,
+                            int32_t final_act, float* out, void* workspace, int64_t workspace_bytes,
+                            int32_t flags, const float* scale1, const float* shift1, void* stream);
 /* Thin outermost layers of unet_256 on the bf16 path (csrc/edge.hip): HBM-bound kernels, one MFMA per 16 pixels, the
  * thin operand read as planar f32 and rounded to bf16 in registers (replace the channel-padded adn_igemm / adn_wgrad
  * calls of the first Conv2d(2->64,k4,s2,p1) and the last ConvTranspose2d(128->1,k4,s2,p1),
@@ -565,7 +573,9 @@ int adn_l0_forward_stats(const float* x, const float* w, const float* bias, int3
 /* adn_d0_dgrad: dz f32 [B][2Hs][2Ws] (gradient of the 1-channel output before the final activation), w f32 [128][16]
  *   ([Cin][kh][kw][1]); seg0 / seg1 = skip / up half of the 128 input channels (64 each, bf16 NHWC): out0 = dIn masked
  *   by ref > 0 (else * slope); seg1 may carry BatchNorm-backward statistics (z, mean, istd, partials: one row of
- *   [2][64] per workgroup, adn_d0_dgrad_num_partials rows).  Ws % 16 == 0. */
+ *   [2][64] per workgroup, adn_d0_dgrad_num_partials rows).  Ws % 16 == 0.
+ *   seg1 without ref: masked by bf16(max(z * scale + shift, 0)) > 0 (seg1->z, scale, shift), the tensor adn_bn_act's
+ *   relu copy would hold for z: the same bits as with that tensor as ref, without it (see adn_convt_n1_forward_bn). */
 int64_t adn_d0_dgrad_num_partials(int32_t B, int32_t Hs, int32_t Ws);
 int adn_d0_dgrad(const float* dz, const float* w, int32_t B, int32_t Hs, int32_t Ws, const AdnEpiSeg* seg0,
                  const AdnEpiSeg* seg1, void* stream);
@@ -574,7 +584,10 @@ int adn_d0_dgrad(const float* dz, const float* w, int32_t B, int32_t Hs, int32_t
  *   last transposed conv (thin = dz); (2, 64, 0): of the first conv (plain = its output gradient, thin = the network
  *   input).  Deterministic (per-workgroup slabs in the workspace + fixed-order sum).  Ws % 32 == 0.
  *   adn_thin_wgrad_ex, relu_plain0 != 0 (ct_n = 1 only): plain0 holds the values before the ReLU and is clamped after
- *   the load, as ADN_N1_RELU_IN0 does for the forward of the same layer.  adn_thin_wgrad = relu_plain0 0. */
+ *   the load, as ADN_N1_RELU_IN0 does for the forward of the same layer.  adn_thin_wgrad = relu_plain0 0.
+ *   adn_thin_wgrad_bn, scale1 / shift1 (f32 [c1], both or neither; ct_n = 1 only): plain1 holds the raw conv output z
+ *   of a train-mode BatchNorm + ReLU layer and is replaced after the load by bf16(max(z * scale1 + shift1, 0)), what
+ *   adn_bn_act's relu copy would hold (see adn_convt_n1_forward_bn).  NULL / NULL: exactly _ex. */
 int64_t adn_thin_wgrad_workspace_bytes(int32_t B, int32_t Hs, int32_t Ws, int32_t ct_n, int32_t c0, int32_t c1);
 int adn_thin_wgrad(const float* thin, int32_t ct_n, const void* plain0, int32_t c0, const void* plain1,
                    int32_t c1, int32_t B, int32_t Hs, int32_t Ws, float* dw, void* workspace,
@@ -582,6 +595,10 @@ int adn_thin_wgrad(const float* thin, int32_t ct_n, const void* plain0, int32_t 
 int adn_thin_wgrad_ex(const float* thin, int32_t ct_n, const void* plain0, int32_t c0, const void* plain1,
                       int32_t c1, int32_t B, int32_t Hs, int32_t Ws, float* dw, void* workspace,
                       int64_t workspace_bytes, int32_t relu_plain0, void* stream);
+int adn_thin_wgrad_bn(const float* thin, int32_t ct_n, const void* plain0, int32_t c0, const void* plain1,
+                      int32_t c1, int32_t B, int32_t Hs, int32_t Ws, float* dw, void* workspace,
+                      int64_t workspace_bytes, int32_t relu_plain0, const float* scale1, const float* shift1,
+                      void* stream);
 /* sum over n f32/dtype elements into one f32 (bias gradient of the outermost ConvTranspose2d). */
 int adn_sum_to_scalar(const void* x, int64_t n, int32_t dtype, float* out, void* workspace,
                       int64_t workspace_bytes, void* stream);
